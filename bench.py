@@ -2,12 +2,16 @@
 """X^2-VLM pre-training step throughput on MI355X: image-text pairs/s (fwd+bwd), X2VLM-base, 224 px,
 per-GPU batch 64, 30-token captions, ITC+ITM+MLM losses (BASELINE.json metric / configs[1]).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N>1 is launched by torch.distributed.run (one rank per GPU, RCCL): gradients are all-reduced in
 buckets overlapped with backward, the ITC features are all-gathered; weak scaling (64 pairs/GPU).
-Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel (the bf16 MFMA GEMM) against
-the 2.5 PFLOP/s dense bf16 peak from HIP-event timings of its launches; `cpu_baseline` times the
-CPU oracle (oracle/, the validated restatement of the reference) on this box's host cores.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the
+headline figure.  --full adds everything else: the hipGraph canary, `roofline` (the dominant kernel,
+the bf16 MFMA GEMM, priced against the 2.5 PFLOP/s dense bf16 peak from HIP-event timings of its
+launches), the unpatched Pretrain.py call sequence, `cpu_baseline` (the CPU oracle - oracle/, the
+validated restatement of the reference - on this box's host cores) and the other configurations.
+--dump-outputs DIR writes what the last timed step computed (losses, per-parameter gradient norms,
+a fixed sample of gradient elements) as DIR/<name>.npy, for comparing two builds output for output.
 """
 import argparse
 import importlib
@@ -139,7 +143,8 @@ def other_configs(args):
     import subprocess
     res = {}
     for name, steps in (("large", 10), ("video", 15), ("region", 15), ("mixed", 10)):
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(steps), "--warmup", "3", "--graph", args.graph]
+        cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(steps), "--warmup", "3", "--graph", args.graph,
+               "--full"]
         if args.no_cpu_baseline:
             cmd.append("--no-cpu-baseline")
         if args.no_graph:
@@ -161,7 +166,7 @@ def other_configs(args):
 
 def with_collectives(args):
     """The base step at ONE rank with the collectives of the N > 1 step issued for real (X2_DDP_SINGLE_RANK_COLLECTIVES=1: ITC all-gathers
-    and the per-segment gradient all-reduces over a one-rank RCCL group), by a child run of this script."""
+    and the per-segment gradient all-reduces over a one-rank RCCL group), by a plain child run of this script."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--graph", args.graph,
            "--no-cpu-baseline", "--no-other-configs"]
@@ -175,6 +180,35 @@ def with_collectives(args):
                         "X2_DDP_SINGLE_RANK_COLLECTIVES=1): host time to enqueue a step incl. the RCCL calls between the segments"}
     except Exception as e:      # noqa: BLE001 - the headline line must still be printed
         return {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
+
+
+DUMP_SAMPLE = 2048      # gradient elements kept per parameter by --dump-outputs (all of them for smaller parameters)
+DUMP_LIMIT = 64 << 20   # bytes, all files together
+
+
+def dump_outputs(out_dir, loss, model):
+    """What a caller of the timed step receives after it: the loss dict and p.grad of every parameter.  Writes one
+    <loss name>.npy (float64 scalar) per loss, grad_norms.npy (float64, the L2 norm of every gradient, named_parameters order)
+    and grad_sample.npy (float32: per gradient, the elements at DUMP_SAMPLE indices drawn from a generator seeded once with
+    0, so the same indices in every run).  -> the list of file names."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(float(v), dtype=np.float64) for k, v in loss.items()}
+    g = torch.Generator().manual_seed(0)
+    norms, sample = [], []
+    for _, p in model.named_parameters():
+        if p.grad is None:
+            continue
+        flat = p.grad.detach().reshape(-1)
+        norms.append(flat.double().norm())
+        idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g) if flat.numel() > DUMP_SAMPLE else torch.arange(flat.numel())
+        sample.append(flat[idx.to(flat.device)].float())
+    arrays["grad_norms"] = torch.stack(norms).cpu().numpy()
+    arrays["grad_sample"] = torch.cat(sample).cpu().numpy()
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT, "--dump-outputs: over %d bytes" % DUMP_LIMIT
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(k + ".npy" for k in arrays)
 
 
 def main():
@@ -201,7 +235,15 @@ def main():
     ap.add_argument("--serialize", action="store_true",
                     help="profiling aid: one HIP stream only (no concurrent text tower / weight-gradient stream), so that "
                          "per-kernel durations are not inflated by co-running kernels")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the hipGraph canary, the roofline, the unpatched Pretrain.py call sequence, "
+                         "cpu_baseline and (N = 1, --config base) the other configurations; off: only what the headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (losses, gradient norms, a fixed gradient sample) "
+                         "as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     conf = CONFIGS[args.config]
     args.batch = args.batch or conf["batch"]
 
@@ -314,22 +356,25 @@ def main():
         torch.cuda.synchronize()
 
     def timed_gemms(n_steps):
-        """HIP events around every GEMM launch of n eager steps (rank 0 times; every rank runs them: the step contains
-        collectives), on the stream each launch goes to.  -> {kernel: (ms, flops, launches)}"""
-        if rank == 0:
+        """HIP events around every GEMM launch of n eager steps (rank 0 times, with --full; every rank runs them: the step contains
+        collectives), on the stream each launch goes to.  -> {kernel: (ms, flops, launches)}.  Without --full the same eager steps
+        run untimed: they draw host and device random numbers, so keeping them gives the captured steps the dropout seeds and
+        hard negatives of a --full run."""
+        timing = rank == 0 and args.full
+        if timing:
             K.GEMM_TIMER = []
         for _ in range(n_steps):
             eager_step()
         torch.cuda.synchronize()
         stat = {}
-        if rank == 0:
+        if timing:
             recs, K.GEMM_TIMER = K.GEMM_TIMER, None
             for a, b, f, name in recs:
                 ms, fl, n = stat.get(name, (0.0, 0.0, 0))
                 stat[name] = (ms + a.elapsed_time(b), fl + f, n + 1)
         return stat
 
-    # ---- untimed: eager warm-up, then the dominant kernel's launch durations from eager steps.  Dominant kernel = the bf16
+    # ---- untimed: eager warm-up, then (--full) the dominant kernel's launch durations from eager steps.  Dominant kernel = the bf16
     # MFMA NT GEMM (7.56 of the 11.74 TFLOP of a base step).  `isolated`: one HIP stream only, so a launch's events see that
     # kernel alone - the number a rocprofv3 kernel trace of `bench.py --serialize` reproduces, and the headline roofline
     # figure; `concurrent`: the shipping three-stream schedule, where a launch also waits for CUs held by other streams.
@@ -353,10 +398,11 @@ def main():
     graph = importlib.import_module("x2-vlm_amd.graph")
     fresh = None
     use_graph = not args.no_graph and (world == 1 or args.graph == "segments")
-    if use_graph and os.environ.get("X2_GRAPH_CANARY", "1") == "1" and not args.tiny and world == 1:
+    if use_graph and os.environ.get("X2_GRAPH_CANARY", "1" if args.full else "0") == "1" and not args.tiny and world == 1:
         # Stream capture leans on ROCm behaviour found by probing (graph.py): a runtime that breaks it tends to crash
         # inside hipStreamEndCapture, which cannot be caught in-process.  A 2-layer copy of this step is captured in a child
         # process first (~10 s); if that does not come back with a hipgraph launch mode the benchmark launches eagerly.
+        # --full only (X2_GRAPH_CANARY=1 / 0 overrides): a plain run captures directly.
         import subprocess
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--tiny", "--config", args.config, "--batch", "4", "--steps", "1",
@@ -433,12 +479,16 @@ def main():
         print("segment times (ms): " + json.dumps({k: round(v, 3) for k, v in runner.segment_times().items()}), file=sys.stderr, flush=True)
     pairs_s = world * units * args.steps / dt
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
+    dumped = None
+    if args.dump_outputs and rank == 0:         # before anything else runs on the model: the last timed step's losses and gradients
+        dumped = dump_outputs(args.dump_outputs, loss, model)
 
-    # ---- the same iteration through the reference's UNPATCHED call sequence (Pretrain.run_image_iter, Pretrain.py:54-76): model(...) ->
+    # ---- (--full) the same iteration through the reference's UNPATCHED call sequence (Pretrain.run_image_iter, Pretrain.py:54-76): model(...) ->
     # optimizer.zero_grad() -> accelerator.backward_step(sum of the losses) on what RocmDDPAccelerator.set_up returns (accelerator._Wrapped:
     # the second call captures the segments, later calls replay them; host-made MLM masks, as the reference's data loader delivers them)
     unpatched = None
-    if world == 1 and args.graph == "segments" and use_graph and not (mixed or region or args.serialize or args.tiny) and os.environ.get("X2_BENCH_UNPATCHED", "1") == "1":
+    if (args.full and world == 1 and args.graph == "segments" and use_graph and not (mixed or region or args.serialize or args.tiny)
+            and os.environ.get("X2_BENCH_UNPATCHED", "1") == "1"):
         try:
             wrapped = acc._Wrapped(model, None)
             a_ = acc.RocmDDPAccelerator(dict(), None)
@@ -472,13 +522,13 @@ def main():
 
     roof = None
     f_min, f_note = conf["f_min"], None
-    if f_min is None:
+    if f_min is None and args.full:
         # executed GEMM FLOPs of one step (NT + TN launches of the instrumented eager steps; the MLM head's recomputed decoder
         # GEMM is not counted), per unit of the metric
         gf = sum(fl for name, (ms, fl, n) in stat_iso.items() if name in ("gemm_nt", "gemm_tn")) / 2 if rank == 0 else 0.0
         f_min = gf / 1e9 / units
         f_note = "measured: 2MNK of the GEMM launches of one step / units per step (attention and row kernels not counted)"
-    if rank == 0:
+    if rank == 0 and args.full:
         def summary(stat, name):
             ms, fl, n = stat.get(name, (0.0, 0.0, 0))
             return None if n == 0 else {"avg_launch_us": round(1e3 * ms / n, 1), "achieved": round(fl / ms / 1e9, 1),
@@ -535,9 +585,11 @@ def main():
             out["roofline"]["also"]["unpatched_pretrain_py"] = unpatched
         out["x2_tune_non_default"] = tuned
         out["env_switches"] = {k: v for k, v in sorted(os.environ.items()) if k.startswith("X2_") and k not in ("X2_BENCH_BACKEND",)}
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            out["outputs"] = {"dir": args.dump_outputs, "files": dumped, "what": "the last timed step's losses and gradients"}
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(conf)
-        if world == 1 and args.config == "base" and not (args.no_other_configs or args.tiny or args.serialize or args.eval_mode):
+        if args.full and world == 1 and args.config == "base" and not (args.no_other_configs or args.tiny or args.serialize or args.eval_mode):
             if args.graph == "segments" and use_graph:
                 out["roofline"]["also"]["host_enqueue_ms_with_collectives"] = with_collectives(args)
             out["other_configs"] = other_configs(args)

@@ -42,3 +42,32 @@ def test_contract_fields_present():
                 '"vs_baseline"', '"dtype"', '"data"', '"config"', '"roofline"', '"cpu_baseline"', '"workload"', '"bound"', '"achieved"',
                 '"peak"', '"frac"', '"traffic"', '"cores"', '"kind"', '"sample"'):
         assert key in src, key
+
+
+def test_plain_and_full_options(tmp_path):
+    """--full (the extra measurements) and --dump-outputs exist; dump_outputs writes float arrays, the same sample in every run."""
+    import importlib.util
+    import subprocess
+    import sys
+
+    import numpy as np
+    import torch
+    r = subprocess.run([sys.executable, SRC, "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout, r.stdout + r.stderr
+    spec = importlib.util.spec_from_file_location("bench_under_test", SRC)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(64, 80), torch.nn.Linear(80, 3), torch.nn.Linear(3, 3, bias=False))
+    model[2].weight.requires_grad_(False)
+    y = model(torch.randn(5, 64)).square().mean()
+    y.backward()
+    files = [bench.dump_outputs(str(tmp_path / d), {"loss_x": y.detach()}, model) for d in ("a", "b")]
+    assert files[0] == files[1] == ["grad_norms.npy", "grad_sample.npy", "loss_x.npy"]
+    for f in files[0]:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    grads = [p.grad for p in model.parameters() if p.grad is not None]
+    assert np.load(tmp_path / "a" / "grad_norms.npy").shape == (len(grads),)
+    assert np.load(tmp_path / "a" / "grad_sample.npy").size == sum(min(g.numel(), bench.DUMP_SAMPLE) for g in grads)
+    assert float(np.load(tmp_path / "a" / "loss_x.npy")) == float(y.detach())
