@@ -38,6 +38,21 @@ def relerr(got, ref):
     return float((got - ref).abs().max() / ref.abs().max().clamp_min(1e-12))
 
 
+def slice_relerr(got, ref, floor=1e-3):
+    """relerr of every slice along dim 0 (a row, a (sequence, head) block) against that slice's own reference max-abs, floored at
+    `floor` x the tensor's max-abs so that a slice of (near) zeros is held to the tensor's scale instead of dividing by ~0: a
+    wrong row or head cannot hide behind a larger one elsewhere in the tensor"""
+    got = got.detach().float().cpu().double().reshape(ref.shape[0], -1)
+    ref = ref.detach().double().reshape(ref.shape[0], -1)
+    den = ref.abs().amax(1).clamp_min(floor * float(ref.abs().max())).clamp_min(1e-30)
+    return float(((got - ref).abs().amax(1) / den).max())
+
+
+def rowerr(got, ref):
+    """slice_relerr of a [rows, D] tensor, row by row"""
+    return slice_relerr(got, ref)
+
+
 @pytest.fixture(params=[(1, 1, 0), (1, 2, 0), (1, 3, 0), (1, 4, 0), (3, 8, 0), (3, 7, 0), (3, 6, 0), (3, 5, 0), (0, 0, 3), (0, 0, 4), (0, 0, 5), (0, 0, 6)],
                 ids=["tile128x128", "tile192x128", "tile64x128", "tile160x128", "nt256x256", "nt224x256", "nt192x256", "nt160x256",
                      "pingpong96x256", "pingpong128x256", "pingpong160x256", "pingpong192x256"])
@@ -355,6 +370,9 @@ def run_attention(K, B, Bkv, H, Lq, Lk, use_bias, use_mask, kv_map, seed, bias_l
     out = attn_ref(q, k0[idx], v0[idx], scale, add)
     out.backward(doh.float().view(B, Lq, H, d).permute(0, 2, 1, 3))
     ref_out = out.permute(0, 2, 1, 3).reshape(B, Lq, H * d)
+    # per (sequence, head) slice, against the slice's own max-abs (floor: 5 % of the tensor's - a K/V batch nobody attends to has zero gradient)
+    bh = lambda t, B_, L_: t.detach().float().cpu().reshape(B_, L_, H, d).permute(0, 2, 1, 3).reshape(B_ * H, L_ * d)
+    sl_err = lambda got_, ref_, B_, L_: slice_relerr(bh(got_, B_, L_), bh(ref_, B_, L_), floor=0.05)
     # ---- HIP ----
     # (transposed bias: whole 128-query chunks for the long one-pass backward, as round_up(577, 64) = 640 happens to be; `narrow_biasT` keeps 64)
     Lkp, Lqp = K.round_up(Lk, 64), K.round_up(Lq, 128 if Lq > 208 and not narrow_biasT else 64)
@@ -384,6 +402,7 @@ def run_attention(K, B, Bkv, H, Lq, Lk, use_bias, use_mask, kv_map, seed, bias_l
         K.attn_fwd(K.view3(qd, B, Lq), K.view3(kd, Bkv, Lk), K.view3(vd, Bkv, Lk), B, Bkv, H, Lq, Lk, scale,
                    K.view3(od, B, Lq), lse, **{k_: v_ for k_, v_ in kw.items() if k_ not in drop_keys})
         assert relerr(od.view(B, Lq, H * d), ref_out) < 8e-3 and bool(torch.isfinite(lse).all())
+        assert sl_err(od, ref_out, B, Lq) < 8e-3
     tol = 1.5e-2   # P and dS are rounded to bf16 before the second MFMA
     want = (q.grad.permute(0, 2, 1, 3).reshape(B, Lq, H * d), k0.grad.permute(0, 2, 1, 3).reshape(Bkv, Lk, H * d),
             v0.grad.permute(0, 2, 1, 3).reshape(Bkv, Lk, H * d))
@@ -401,9 +420,11 @@ def run_attention(K, B, Bkv, H, Lq, Lk, use_bias, use_mask, kv_map, seed, bias_l
         assert relerr(dq.view(B, Lq, H * d), want[0]) < tol
         assert relerr(dk.view(Bkv, Lk, H * d), want[1]) < tol
         assert relerr(dv.view(Bkv, Lk, H * d), want[2]) < tol
+        assert sl_err(dq, want[0], B, Lq) < tol and sl_err(dk, want[1], Bkv, Lk) < tol and sl_err(dv, want[2], Bkv, Lk) < tol
         assert bool(torch.isfinite(delta).all())
         if use_bias:
             assert relerr(dS[..., :Lk].float().sum(0), bias_leaf.grad) < tol
+            assert slice_relerr(dS[..., :Lk].float().sum(0), bias_leaf.grad, floor=0.05) < tol      # head by head
     got = backward()
     check(*got)
     if backward(ask_form=True) in (1, 3):
@@ -554,6 +575,19 @@ def test_attention_long_one_pass_backward_shapes(K):
     run_attention(K, B=1, Bkv=1, H=2, Lq=300, Lk=300, use_bias=True, use_mask=False, kv_map=None, seed=750, narrow_biasT=True)
 
 
+def test_attention_past_the_long_one_pass_limits(K):
+    """Past LP_MAX_LQ = 640 queries or LP_MAX_LK = 768 keys the long one-pass backward steps aside and the 8-wave dQ + dK/dV pair runs (form 0):
+    one past each limit and past both, N = 1025 and N = 2305 (768 px) with the bias in both units; and X2VLM-large's cross-attention, 30 text
+    rows over 577 image tokens that several rows share (attn_bwd_dq_kernel<2, 1, false> + the 4-wave dK/dV kernel over the CSR)."""
+    run_attention(K, B=1, Bkv=1, H=2, Lq=641, Lk=641, use_bias=True, use_mask=False, kv_map=None, seed=800)
+    run_attention(K, B=1, Bkv=1, H=2, Lq=640, Lk=769, use_bias=True, use_mask=True, kv_map=None, seed=810)
+    run_attention(K, B=1, Bkv=1, H=2, Lq=641, Lk=769, use_bias=True, use_mask=False, kv_map=None, seed=820, bias_log2=True)
+    for log2 in (False, True):
+        run_attention(K, B=1, Bkv=1, H=2, Lq=1025, Lk=1025, use_bias=True, use_mask=False, kv_map=None, seed=830, bias_log2=log2)
+        run_attention(K, B=1, Bkv=1, H=2, Lq=2305, Lk=2305, use_bias=True, use_mask=False, kv_map=None, seed=840, bias_log2=log2)
+    run_attention(K, B=4, Bkv=2, H=2, Lq=30, Lk=577, use_bias=False, use_mask=True, kv_map=[1, 0, 1, 1], seed=850)
+
+
 def test_attention_long_one_pass_at_the_full_size_of_x2vlm_large(K):
     """BASELINE configs[3] on one GPU: batch 32 x 16 heads x N = 577 (512 workgroups = two rounds of the chip, 84 MB of dQ partials in the workspace,
     the XCD-aware block order over 16 heads): the oracle does not reach this size in test time, so the long one-pass backward is held against the
@@ -592,35 +626,46 @@ def test_attention_long_one_pass_at_the_full_size_of_x2vlm_large(K):
     assert torch.equal(one[0], again[0]) and torch.equal(one[1], again[1]) and torch.equal(one[2], again[2])
 
 
-@pytest.mark.parametrize("rows,D,period", [(37, 768, 0), (788, 768, 0), (4 * 196, 768, 196), (50, 128, 0), (9, 1536, 0)])
+@pytest.mark.parametrize("rows,D,period", [(37, 768, 0), (788, 768, 0), (4 * 196, 768, 196), (50, 128, 0), (9, 1536, 0),
+                                           # NV = 4 and 8 (X2VLM-large, its 2 x 1024 MLP heads), ragged last lane groups (250 / 385 float4 per row)
+                                           (1154, 1024, 0), (300, 2048, 0), (200, 1000, 0), (40, 1540, 0),
+                                           # the step's row counts: base vision 64 x 197 (whole, and without the cls rows), large 32 x 577
+                                           (12608, 768, 0), (64 * 196, 768, 196), (18464, 1024, 0),
+                                           # edges of the 16-row backward workgroup
+                                           (1, 2048, 0), (15, 1024, 0), (16, 768, 0), (17, 1000, 0)])
 def test_layernorm(K, rows, D, period):
+    """x2_layernorm_fwd / _bwd (every backward mode: fp32 dy, bf16 dy, dcol, post= with and without a row scale) against float64
+    autograd, per tensor and row by row."""
     total = rows if period == 0 else rows // period * (period + 1)
     x = rnd(total, D, seed=1, scale=2.0) + 0.5
     w, b = rnd(D, seed=2) * 0.1 + 1, rnd(D, seed=3) * 0.1
     dy = rnd(total, D, seed=4)
     sel = torch.arange(total) if period == 0 else torch.tensor([r + r // period + 1 for r in range(rows)])
-    xl = x.clone().requires_grad_(True); wl = w.clone().requires_grad_(True); bl = b.clone().requires_grad_(True)
+    xl = x.double().requires_grad_(True); wl = w.double().requires_grad_(True); bl = b.double().requires_grad_(True)
     ref = O.layer_norm(xl[sel], wl, bl, 1e-6)
-    ref.backward(dy[sel])
+    ref.backward(dy.double()[sel])
     yb, yf, mean, rstd = K.layernorm_fwd(x.to(dev), w.to(dev), b.to(dev), 1e-6, rows=rows, period=period, want_f32=True)
     assert relerr(yf[sel], ref) < 1e-5 and relerr(yb[sel], ref) < 6e-3
+    assert rowerr(yf[sel], ref) < 1e-5 and rowerr(yb[sel], ref) < 6e-3
     dw, db = torch.zeros(D, device=dev), torch.zeros(D, device=dev)
     dres = rnd(total, D, seed=5)
     dx, dxb = K.layernorm_bwd(dy.to(dev), x.to(dev), mean, rstd, w.to(dev), dw, db, dres=dres.to(dev), period=period,
                               want_bf16=True)
-    assert relerr(dx[sel], xl.grad[sel] + dres[sel]) < 2e-5
+    assert relerr(dx[sel], xl.grad[sel] + dres[sel]) < 2e-5 and rowerr(dx[sel], xl.grad[sel] + dres[sel]) < 2e-5
     assert relerr(dxb[sel], xl.grad[sel]) < 6e-3          # bf16 copy = gradient of the LN input alone (feeds the producing linear)
+    assert rowerr(dxb[sel], xl.grad[sel]) < 6e-3
     assert relerr(dw, wl.grad) < 2e-5 and relerr(db, bl.grad) < 2e-5
     # bf16 incoming gradient (input-gradient GEMMs of the pre-LN blocks write bf16): same arithmetic on the rounded values
     dyb = bf(dy)
-    xl2 = x.clone().requires_grad_(True)
-    O.layer_norm(xl2[sel], w, b, 1e-6).backward(dyb.float()[sel])
+    xl2 = x.double().requires_grad_(True)
+    O.layer_norm(xl2[sel], w.double(), b.double(), 1e-6).backward(dyb.double()[sel])
     dwb, dbb = torch.zeros(D, device=dev), torch.zeros(D, device=dev)
     dxh, _ = K.layernorm_bwd(dyb.to(dev), x.to(dev), mean, rstd, w.to(dev), dwb, dbb, dres=dres.to(dev), period=period)
-    assert relerr(dxh[sel], xl2.grad[sel] + dres[sel]) < 2e-5
+    assert relerr(dxh[sel], xl2.grad[sel] + dres[sel]) < 2e-5 and rowerr(dxh[sel], xl2.grad[sel] + dres[sel]) < 2e-5
     dw2, db2, dcol = torch.zeros(D, device=dev), torch.zeros(D, device=dev), torch.zeros(D, device=dev)
     dx2, _ = K.layernorm_bwd(dy.to(dev), x.to(dev), mean, rstd, w.to(dev), dw2, db2, dcol=dcol, period=period)
     assert relerr(dcol, xl.grad[sel].sum(0)) < 5e-5 and relerr(dx2[sel], xl.grad[sel]) < 2e-5
+    assert rowerr(dx2[sel], xl.grad[sel]) < 2e-5
     if period == 0:
         # by-products of the FINAL output for the layer scale below (post=): bf16(r * (dx + dres)) and its column sums
         for rs in (None, (torch.rand(total, generator=torch.Generator().manual_seed(9)) > 0.2).float() * 1.25):
@@ -629,7 +674,7 @@ def test_layernorm(K, rows, D, period):
                                         post=(None if rs is None else rs.to(dev), cs))
             want = (xl2.grad + dres) * (1.0 if rs is None else rs[:, None])
             assert relerr(dx3, dxh.cpu()) < 1e-6 and relerr(dw3, dwb.cpu()) < 1e-6 and relerr(db3, dbb.cpu()) < 1e-6
-            assert relerr(dx3b, want) < 6e-3 and relerr(cs, want.sum(0)) < 2e-5
+            assert relerr(dx3b, want) < 6e-3 and relerr(cs, want.sum(0)) < 2e-5 and rowerr(dx3b, want) < 6e-3
 
 
 def test_colsum_layerscale_casts(K):
