@@ -252,6 +252,34 @@ int x2_sample_negatives(const float* sim, int n, const long* group, const float*
 /* additive key mask of BertModel (get_extended_attention_mask: neg = -10000; invert_attention_mask: -1e9; xbert.py:1105-1160):
  * out[s][l] = (1 - atts[s][l]) * neg, l < L; 0 in the pad columns L..Lp-1 (the attention kernels read [S][Lp], Lp % 64 == 0) */
 int x2_additive_mask(const long* atts, float* out, int S, int L, int Lp, float neg, void* stream);
+
+/* ---- captioning fine-tune (XVLMForMLMCaptioning): additive to ABI v14 - no existing signature or struct changes, x2_abi_version() stays 14 ----
+ *   x2_attn_fwd_mask2d / x2_attn_bwd_mask2d : x2_attn_fwd / x2_attn_bwd for BERT self-attention with a per-sequence additive mask
+ *       mask2d[B][Lq][mask2d_ld] fp32 read per (query, key) (x2_additive_mask2d builds it); Lq == Lk <= 128, B == Bkv, head_dim 64, H any;
+ *       args->bias / biasT / mask / kv_idx / seq_off / dS must be NULL and dbg 0 (key padding is what the 2-D mask expresses); dropout and
+ *       LSE / Delta as x2_attn_fwd / x2_attn_bwd; the backward takes phase 0 only and has no atomics
+ *   x2_additive_mask2d : out[s][i][j] = (1 - m[s][i][j]) * neg (j < L), 0 for L <= j < Lp; m [S][L][L] int64
+ *   x2_embed_fwd_pid / x2_embed_bwd_pid : x2_embed_fwd / _bwd with explicit position ids pids[R] (int64) instead of r % L:
+ *       out[r] = word[ids[r]] + pos[pids[r]] + type0;  dword[ids[r]] += g[r], dpos[pids[r]] += g[r], dtype0 += g[r] (fixed order, no atomics;
+ *       L = row period of the scratch totals, scratch of min(L, R) * D floats)
+ *   x2_mlm_ls_fwd : x2_mlm_ce_fwd plus sumz[R][Vp/64] (sum of z over each chunk's valid columns) and zign[R] = z[r][ignore]
+ *   x2_ls_combine : label-smoothed KL (q[label] = 1 - ls, q[c] = ls / (V - 2), q[ignore] = 0, q = 0 on rows whose label is ignore):
+ *       lse[r], kl_row[r], out2 = {sum_r kl_row[r] * w[r] / (sum w + 1e-5), sum w}
+ *   x2_mlm_ls_bwd : dl[R][ldd] bf16 = (sum(q) * softmax(z) - q) * gscale * g[0] * w[r] / (stat[1] + 1e-5), 0 on ignored rows and pad columns */
+int x2_attn_fwd_mask2d(const X2AttnArgs* args, const float* mask2d, int mask2d_ld, void* stream);
+int x2_attn_bwd_mask2d(const X2AttnArgs* args, const float* mask2d, int mask2d_ld, void* stream);
+int x2_additive_mask2d(const long* m, float* out, int S, int L, int Lp, float neg, void* stream);
+int x2_embed_fwd_pid(const long* ids, const long* pids, const float* word, const float* pos, const float* type0, float* out, int R, int D,
+                     void* stream);
+int x2_embed_bwd_pid(const long* ids, const long* pids, const float* g, float* dword, float* dpos, float* dtype0, int R, int L, int D,
+                     float* scratch, void* stream);
+int x2_mlm_ls_fwd(const void* X, const void* E, const float* bias, const long* labels, long ignore, int R, int Vp, int V, int Hd, int ldx,
+                  int lde, float* part, float* sumz, float* zlab, float* zign, void* stream);
+int x2_ls_combine(const float* part, const float* sumz, int chunks, const float* zlab, const float* zign, const long* labels, const float* w,
+                  int R, int V, long ignore, float ls, float* lse, float* kl_row, float* out2, void* stream);
+int x2_mlm_ls_bwd(const void* X, const void* E, const float* bias, const long* labels, const float* w, const float* lse, const float* g,
+                  const float* stat, float gscale, float ls, long ignore, int R, int Vp, int V, int Hd, int ldx, int lde, void* dl_bf16,
+                  long ldd, void* stream);
 /* CSR "K/V batch -> query sequences using it" from kv[S] (values in [0, Bi)): off[Bi+1], order[S] (stable counting sort);
  * the seq_off / seq_ids tables of X2AttnArgs for rows that share an image's K/V (the 4-pass fusion batch) */
 int x2_kv_csr(const int* kv, int S, int Bi, int* off, int* order, void* stream);

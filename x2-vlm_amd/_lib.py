@@ -76,6 +76,15 @@ _SIGS = {
     "x2_grad_norm": [P, I, I, F, P, P, P],
     "x2_adamw_multi": [P, I, I, P, P, I, F, F, F, P, P],
     "x2_colsum_f32": [P, P, I, I, P],
+    # captioning fine-tune (additive to ABI v14)
+    "x2_attn_fwd_mask2d": [C.POINTER(AttnArgs), P, I, P],
+    "x2_attn_bwd_mask2d": [C.POINTER(AttnArgs), P, I, P],
+    "x2_additive_mask2d": [P, P, I, I, I, F, P],
+    "x2_embed_fwd_pid": [P, P, P, P, P, P, I, I, P],
+    "x2_embed_bwd_pid": [P, P, P, P, P, P, I, I, I, P, P],
+    "x2_mlm_ls_fwd": [P, P, P, P, L, I, I, I, I, I, I, P, P, P, P, P],
+    "x2_ls_combine": [P, P, I, P, P, P, P, I, I, L, F, P, P, P, P],
+    "x2_mlm_ls_bwd": [P, P, P, P, P, P, P, P, F, F, L, I, I, I, I, I, I, P, L, P],
 }
 # communicator entry points (csrc/comm.hip): explicit stream / event arguments, bound without the implicit stream of call()
 _COMM_SIGS = {

@@ -159,7 +159,9 @@ __device__ __forceinline__ f32x4 apply_bias_mask(f32x4 s, float4 bb, float4 mm, 
   o[3] = key0 + 3 < Lk ? s[3] * sc2 + (bb.w + mm.w) * LOG2E : NEG_BIG;
   return o;
 }
-template <int QG, bool BL2 = false>
+// M2D (x2_attn_fwd_mask2d / x2_attn_bwd_mask2d only): `bias` holds a per-SEQUENCE additive mask [B][Lq][bias_ld] read per (query, key),
+// the 2-D text mask of the captioning fine-tune (tril / FG-free), instead of the per-head [H][Lq][bias_ld] relative-position bias
+template <int QG, bool BL2 = false, bool M2D = false>
 __device__ __forceinline__ void load_bias_mask(const AttnArgs& a, int h, int b, const int (&q)[QG], int key_base, int g, int nsub,
                                                float4 (&bb)[QG][4], float4 (&mm)[4]) {
 #pragma unroll
@@ -173,7 +175,7 @@ __device__ __forceinline__ void load_bias_mask(const AttnArgs& a, int h, int b, 
     for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
       for (int gq = 0; gq < QG; ++gq)
-        if (nt < nsub) bb[gq][nt] = *reinterpret_cast<const float4*>(a.bias + ((long)h * a.Lq + q[gq]) * a.bias_ld + key_base + nt * 16 + g * 4);
+        if (nt < nsub) bb[gq][nt] = *reinterpret_cast<const float4*>(a.bias + ((M2D ? (long)b : (long)h) * a.Lq + q[gq]) * a.bias_ld + key_base + nt * 16 + g * 4);
     // a bias in log2 units (dbg bit 4) reaching a kernel that has no one-fma form (the callers of this function multiply by
     // log2 e themselves): back to natural units here, a wave-uniform branch outside the per-score arithmetic
     if (!BL2 && (a.dbg & 16)) {
@@ -197,7 +199,7 @@ __device__ __forceinline__ void load_bias_mask(const AttnArgs& a, int h, int b, 
 // NS: LDS slots.  Resident form: one per key tile (4 covers Lk <= 256; 1 for Lk <= 64, the 30-token text sequences: 16 KB
 // per workgroup instead of 32-64 KB lets 10 of the 2-wave workgroups share a CU instead of 5, and these launches are a
 // serial load -> multiply -> store chain per workgroup whose only latency hiding is other workgroups).
-template <int QW, int QG, bool RES, int NS = (RES ? 4 : 2), int WPS = (QG > 1 ? 2 : 4), bool BL2 = false>     // WPS: waves per SIMD the registers must allow
+template <int QW, int QG, bool RES, int NS = (RES ? 4 : 2), int WPS = (QG > 1 ? 2 : 4), bool BL2 = false, bool M2D = false>     // WPS: waves per SIMD the registers must allow
 __global__ __launch_bounds__(64 * QW, WPS) void attn_fwd_kernel(AttnArgs a) {
   const DropSpec drop_ = drop_at_epoch(a.drop, a.drop_epoch);
   constexpr int NT = 64 * QW;
@@ -265,7 +267,7 @@ __global__ __launch_bounds__(64 * QW, WPS) void attn_fwd_kernel(AttnArgs a) {
     }
     const int nsub = FULL ? 4 : (idle ? 0 : min(4, (a.Lk - kt * KT + 15) >> 4));      // valid 16-key sub-tiles of this tile (wave-uniform)
     float4 bbv[QG][4], mmv[4];
-    load_bias_mask<QG, BL2>(a, h, b, q, kt * KT, g, nsub, bbv, mmv);
+    load_bias_mask<QG, BL2, M2D>(a, h, b, q, kt * KT, g, nsub, bbv, mmv);
     f32x4 st[QG][4];
 #pragma unroll
     for (int gq = 0; gq < QG; ++gq)
@@ -351,7 +353,7 @@ __global__ __launch_bounds__(64 * QW, WPS) void attn_fwd_kernel(AttnArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------ backward: dQ (+ dS)
-template <int QW, int QG, bool RES, int NS = (RES ? 4 : 2), int WPS = (QG > 1 ? 2 : 4), bool BL2 = false>
+template <int QW, int QG, bool RES, int NS = (RES ? 4 : 2), int WPS = (QG > 1 ? 2 : 4), bool BL2 = false, bool M2D = false>
 __global__ __launch_bounds__(64 * QW, WPS) void attn_bwd_dq_kernel(AttnArgs a) {
   const DropSpec drop_ = drop_at_epoch(a.drop, a.drop_epoch);
   constexpr int NT = 64 * QW;
@@ -421,7 +423,7 @@ __global__ __launch_bounds__(64 * QW, WPS) void attn_bwd_dq_kernel(AttnArgs a) {
     }
     const int nsub = FULL ? 4 : (idle ? 0 : min(4, (a.Lk - kt * KT + 15) >> 4));
     float4 bbv[QG][4], mmv[4];
-    load_bias_mask<QG, BL2>(a, h, b, q, kt * KT, g, nsub, bbv, mmv);
+    load_bias_mask<QG, BL2, M2D>(a, h, b, q, kt * KT, g, nsub, bbv, mmv);
     f32x4 ds[QG][4];
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
@@ -812,7 +814,7 @@ __global__ __launch_bounds__(64 * QW, 3) void attn_bwd_dq_walk_kernel(AttnArgs a
 
 // ------------------------------------------------------------------------------------------ backward: dK, dV
 // KW waves, KG groups of 16 keys per wave; the workgroup walks every (sequence using this K/V batch, 64-query tile).
-template <int KW, int KG, bool RES, int NS = (RES ? 4 : 2), int WPS = ((KW == 4 && !RES) ? 3 : 4), bool BL2 = false>
+template <int KW, int KG, bool RES, int NS = (RES ? 4 : 2), int WPS = ((KW == 4 && !RES) ? 3 : 4), bool BL2 = false, bool M2D = false>
 // (second launch bound = waves per SIMD the register allocation must allow: these kernels hide their load -> MFMA -> exp
 // chains only behind other waves, and left alone hipcc spends 170-230 VGPRs on the short-sequence forms (2 waves per SIMD);
 // capped at 128 they run 1.3-1.5x faster.  The streamed 4-wave form needs more than 128: 35 spills under the cap.)
@@ -916,7 +918,19 @@ __global__ __launch_bounds__(64 * KW, WPS) void attn_bwd_dkv_kernel(AttnArgs a) 
       for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int gk = 0; gk < KG; ++gk) btv[gk][t] = float4{0.f, 0.f, 0.f, 0.f};
-      if (a.biasT) {
+      if constexpr (M2D) {
+        // the 2-D mask [B][Lq][bias_ld] read down a key's column: four queries per lane, one scalar load each (short text sequences only)
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int gk = 0; gk < KG; ++gk)
+            if (t < nsub) {
+              const float* mc = a.bias + (long)b * a.Lq * a.bias_ld + key[gk];
+              const int qq0 = qt * KT + t * 16 + g * 4;
+              btv[gk][t] = float4{mc[(long)min(qq0 + 0, a.Lq - 1) * a.bias_ld], mc[(long)min(qq0 + 1, a.Lq - 1) * a.bias_ld],
+                                  mc[(long)min(qq0 + 2, a.Lq - 1) * a.bias_ld], mc[(long)min(qq0 + 3, a.Lq - 1) * a.bias_ld]};
+            }
+      } else if (a.biasT) {
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -2029,4 +2043,42 @@ extern "C" int x2_attn_bwd(const AttnArgs* pa, void* stream) {
     hipLaunchKernelGGL((attn_bwd_dkv_kernel<4, 1, false>), dim3((a.Lk + 63) / 64, a.H, a.Bkv), dim3(256), 0, st, a);
   }
   return x2_check_launch("x2_attn_bwd(dkv)");
+}
+
+// ------------------------------------------------------------------------------------------ 2-D masked self-attention (additive to ABI v14)
+// BERT self-attention with a per-sequence [Lq][Lk] additive mask (captioning fine-tune: tril or FG-free, xbert extended mask (1 - m) * -10000):
+// the streamed short-sequence kernels above with M2D set, the mask handed over in `bias` (no relative-position bias exists on this path).
+// Per-key padding is whatever the 2-D mask expresses (args->mask must be NULL).  Dropout, LSE / Delta and the no-atomics backward as x2_attn_fwd /
+// x2_attn_bwd; only these instantiations read a 2-D mask.
+static int check_mask2d(const AttnArgs& a, const float* mask2d, int ld, const char* who) {
+  if (int e = check_common(a, who)) return e;
+  X2_REQUIRE(mask2d && ld % 64 == 0 && ld >= a.Lk, "%s: mask2d [B][Lq][ld] with ld a multiple of 64 covering Lk (ld=%d)", who, ld);
+  X2_REQUIRE(!a.bias && !a.biasT && !a.mask && !a.kv_idx && !a.seq_off && !a.seq_ids && !a.dS && a.dbg == 0,
+             "%s: no bias / per-key mask / K-V sharing / dS / dbg with a 2-D mask", who);
+  X2_REQUIRE(a.Lq == a.Lk && a.Lq <= 128 && a.B == a.Bkv, "%s: self-attention with Lq == Lk <= 128 and B == Bkv (Lq=%d Lk=%d B=%d Bkv=%d)", who,
+             a.Lq, a.Lk, a.B, a.Bkv);
+  return X2_OK;
+}
+extern "C" int x2_attn_fwd_mask2d(const AttnArgs* pa, const float* mask2d, int mask2d_ld, void* stream) {
+  AttnArgs a = *pa;
+  a.grid_nx = a.grid_ny = a.grid_nz = a.grid_map = 0;
+  if (int e = check_mask2d(a, mask2d, mask2d_ld, "x2_attn_fwd_mask2d")) return e;
+  X2_REQUIRE(a.Q && a.K && a.V && a.Out && a.LSE, "x2_attn_fwd_mask2d: null tensor");
+  X2_REQUIRE((a.o_rs % 4 | a.o_bs % 4) == 0, "x2_attn_fwd_mask2d: output strides");
+  a.bias = mask2d; a.bias_ld = mask2d_ld;
+  hipLaunchKernelGGL((attn_fwd_kernel<4, 1, false, 2, 4, false, true>), dim3((a.Lq + 63) / 64, a.H, a.B), dim3(256), 0, (hipStream_t)stream, a);
+  return x2_check_launch("x2_attn_fwd_mask2d");
+}
+extern "C" int x2_attn_bwd_mask2d(const AttnArgs* pa, const float* mask2d, int mask2d_ld, void* stream) {
+  AttnArgs a = *pa;
+  a.grid_nx = a.grid_ny = a.grid_nz = a.grid_map = 0;
+  if (int e = check_mask2d(a, mask2d, mask2d_ld, "x2_attn_bwd_mask2d")) return e;
+  X2_REQUIRE(a.Q && a.K && a.V && a.O && a.dO && a.dQ && a.dK && a.dV && a.LSE && a.Delta, "x2_attn_bwd_mask2d: null tensor");
+  X2_REQUIRE(a.phase == 0, "x2_attn_bwd_mask2d: phase=%d (both halves only)", a.phase);
+  a.bias = mask2d; a.bias_ld = mask2d_ld;
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<4, 1, false, 2, 4, false, true>), dim3((a.Lq + 63) / 64, a.H, a.B), dim3(256), 0, st, a);
+  if (int e = x2_check_launch("x2_attn_bwd_mask2d(dq)")) return e;
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<4, 1, false, 2, 3, false, true>), dim3((a.Lk + 63) / 64, a.H, a.Bkv), dim3(256), 0, st, a);
+  return x2_check_launch("x2_attn_bwd_mask2d(dkv)");
 }

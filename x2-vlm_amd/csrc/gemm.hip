@@ -46,6 +46,13 @@ struct GemmNT {
   float* ce_zlab;           // [M] logit at the label (variant 8)
   float ce_gscale;
   int ce_C;                 // valid columns (vocabulary size; N is padded to a multiple of 64)
+  // label-smoothed MLM loss (epilogue variants 11 / 12, x2_mlm_ls_fwd / _bwd; captioning fine-tune): variant 11 = variant 8 plus the chunk sums of z
+  // and the logit at the ignored class, variant 12 = (sum(q) p - q) * w[row] * g / (sum w + 1e-5) with q the smoothed target (heads.hip ls_combine)
+  float* ce_sumz;           // [M][N / 64] sum of z over the valid columns of every 64-column chunk (variant 11)
+  float* ce_zign;           // [M] logit at column ce_ignore (variant 11)
+  long ce_ignore;           // ignored class (the tokenizer's [CLS] id): q[ignore] = 0, rows whose label is it carry no loss
+  float ce_ls;              // label smoothing
+  const float* ce_w;        // [M] per-row weight (variant 12; ce_stat[1] = sum of the weights)
 };
 
 // logical tile id -> (row tile, col tile): XCD-contiguous chunks, inside a chunk groups of `gm` row panels
@@ -89,6 +96,8 @@ __device__ __forceinline__ void st16(void* p, u32x4 v, bool wt) {
 //     partial row colsum[2 * row tile + wave row][N]; the caller reduces the partial rows (x2_reduce_partials*): replaces a
 //     stand-alone pass over the [M, 4D] gradient (x2_colsum_bf16: 77 MB read per vision block) without the atomics that
 //     made the first fused form slower than that pass
+//  11 = 8 plus the chunk sums of the logits and the logit at the ignored class (x2_mlm_ls_fwd: label-smoothed MLM loss, captioning)
+//  12 bias, then (sum(q) softmax - q) * w[row] * g / (sum w + 1e-5) -> bf16, q the smoothed target (x2_mlm_ls_bwd)
 #ifdef X2_PROBE
 #define NT_DBG(p, bit) (((p).dbg & (bit)) != 0)
 // per-phase time stamps of gemm_nt256_kernel (probe builds only): wave 0 of every workgroup writes wall_clock64() (100 MHz) at
@@ -225,6 +234,43 @@ __device__ __forceinline__ void nt_epilogue(const GemmNT& p, Acc& acc, char* sme
         }
         se += __shfl_xor(se, 1, 64); se += __shfl_xor(se, 2, 64); se += __shfl_xor(se, 4, 64);
         if ((lane & 7) == 0) *reinterpret_cast<float2*>(p.ce_part + ((size_t)m * (p.N >> 6) + (nw0 >> 6)) * 2) = float2{mx, se};
+        continue;
+      }
+      if constexpr (VAR == 11) {
+        // variant 8's chunk statistics, plus sum z over the chunk and z at the ignored class
+        const long lab = p.ce_labels[m];
+        float mx = -INFINITY, sz = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { mx = n + e < p.ce_C ? fmaxf(mx, v[e]) : mx; sz += n + e < p.ce_C ? v[e] : 0.f; }
+        mx = fmaxf(mx, __shfl_xor(mx, 1, 64)); mx = fmaxf(mx, __shfl_xor(mx, 2, 64)); mx = fmaxf(mx, __shfl_xor(mx, 4, 64));
+        sz += __shfl_xor(sz, 1, 64); sz += __shfl_xor(sz, 2, 64); sz += __shfl_xor(sz, 4, 64);
+        float se = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          se += n + e < p.ce_C ? __expf(v[e] - mx) : 0.f;
+          if ((long)(n + e) == lab) p.ce_zlab[m] = v[e];
+          if ((long)(n + e) == p.ce_ignore) p.ce_zign[m] = v[e];
+        }
+        se += __shfl_xor(se, 1, 64); se += __shfl_xor(se, 2, 64); se += __shfl_xor(se, 4, 64);
+        if ((lane & 7) == 0) {
+          *reinterpret_cast<float2*>(p.ce_part + ((size_t)m * (p.N >> 6) + (nw0 >> 6)) * 2) = float2{mx, se};
+          p.ce_sumz[(size_t)m * (p.N >> 6) + (nw0 >> 6)] = sz;
+        }
+        continue;
+      }
+      if constexpr (VAR == 12) {
+        const long lab = p.ce_labels[m];
+        const bool live = lab >= 0 && lab != p.ce_ignore;
+        const float conf = 1.f - p.ce_ls, sm = p.ce_ls / (float)(p.ce_C - 2), qsum = conf + sm * (float)(p.ce_C - 2);
+        const float sc = live ? p.ce_gscale * p.ce_g[0] * p.ce_w[m] / (p.ce_stat[1] + 1e-5f) : 0.f, l = p.ce_lse[m];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const long c = n + e;
+          const float q = c == lab ? conf : (c == p.ce_ignore ? 0.f : sm);
+          v[e] = c < p.ce_C ? (qsum * __expf(v[e] - l) - q) * sc : 0.f;
+        }
+        st16(reinterpret_cast<bf16_t*>(p.C) + (size_t)m * p.ldc + n,
+             u32x4{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7])}, false);
         continue;
       }
       if constexpr (VAR == 9) {
@@ -1367,6 +1413,12 @@ static int launch_nt_ce(GemmNT& p, int var, hipStream_t stream) {
   if (var == 8) {
     if (use64) hipLaunchKernelGGL((gemm_nt_kernel<2, 8>), dim3(t64), dim3(256), 2 * (64 * 128 + TILE_BYTES), stream, p);
     else hipLaunchKernelGGL((gemm_nt_kernel<4, 8>), dim3(t128), dim3(256), GEMM_LDS_BYTES, stream, p);
+  } else if (var == 11) {
+    if (use64) hipLaunchKernelGGL((gemm_nt_kernel<2, 11>), dim3(t64), dim3(256), 2 * (64 * 128 + TILE_BYTES), stream, p);
+    else hipLaunchKernelGGL((gemm_nt_kernel<4, 11>), dim3(t128), dim3(256), GEMM_LDS_BYTES, stream, p);
+  } else if (var == 12) {
+    if (use64) hipLaunchKernelGGL((gemm_nt_kernel<2, 12>), dim3(t64), dim3(256), 2 * (64 * 128 + TILE_BYTES), stream, p);
+    else hipLaunchKernelGGL((gemm_nt_kernel<4, 12>), dim3(t128), dim3(256), GEMM_LDS_BYTES, stream, p);
   } else {
     if (use64) hipLaunchKernelGGL((gemm_nt_kernel<2, 9>), dim3(t64), dim3(256), 2 * (64 * 128 + TILE_BYTES), stream, p);
     else hipLaunchKernelGGL((gemm_nt_kernel<4, 9>), dim3(t128), dim3(256), GEMM_LDS_BYTES, stream, p);
@@ -1396,6 +1448,32 @@ extern "C" int x2_mlm_ce_bwd(const void* X, const void* E, const float* bias, co
            labels, lse, g, stat, nullptr, nullptr, gscale, V};
   launch_nt_ce(p, 9, (hipStream_t)stream);
   return x2_check_launch("x2_mlm_ce_bwd");
+}
+// Label-smoothed, per-row weighted form of the same head (captioning fine-tune; additive to ABI v14).  Forward: part as x2_mlm_ce_fwd plus
+// sumz[R][Vp/64] (chunk sums of z), zlab and zign (z at the ignored class); x2_ls_combine (heads.hip) forms lse and the loss.  Backward:
+// dl = (sum(q) softmax(z) - q) * gscale * g[0] * w[r] / (stat[1] + 1e-5), zero on rows whose label is `ignore` or < 0.
+extern "C" int x2_mlm_ls_fwd(const void* X, const void* E, const float* bias, const long* labels, long ignore, int R, int Vp, int V, int Hd,
+                             int ldx, int lde, float* part, float* sumz, float* zlab, float* zign, void* stream) {
+  X2_REQUIRE(X && E && labels && part && sumz && zlab && zign, "x2_mlm_ls_fwd: null argument");
+  X2_REQUIRE(mlm_ce_shapes_ok(R, Vp, V, Hd, ldx, lde) && V > 2 && ignore >= 0 && ignore < V,
+             "x2_mlm_ls_fwd: R=%d Vp=%d V=%d Hd=%d ldx=%d lde=%d ignore=%ld", R, Vp, V, Hd, ldx, lde, ignore);
+  GemmNT p{(const bf16_t*)X, (const bf16_t*)E, nullptr, bias, nullptr, nullptr, nullptr, R, Vp, Hd, ldx, lde, Vp, 0, 0, 0, 0,
+           g_tune[0] > 0 ? g_tune[0] : 8, DropSpec{0u, 0u, 1.f}, nullptr, nullptr, nullptr, 0, 0,
+           labels, nullptr, nullptr, nullptr, part, zlab, 1.f, V, sumz, zign, ignore, 0.f, nullptr};
+  launch_nt_ce(p, 11, (hipStream_t)stream);
+  return x2_check_launch("x2_mlm_ls_fwd");
+}
+extern "C" int x2_mlm_ls_bwd(const void* X, const void* E, const float* bias, const long* labels, const float* w, const float* lse, const float* g,
+                             const float* stat, float gscale, float ls, long ignore, int R, int Vp, int V, int Hd, int ldx, int lde, void* dl_bf16,
+                             long ldd, void* stream) {
+  X2_REQUIRE(X && E && labels && w && lse && g && stat && dl_bf16, "x2_mlm_ls_bwd: null argument");
+  X2_REQUIRE(mlm_ce_shapes_ok(R, Vp, V, Hd, ldx, lde) && ldd >= Vp && ldd % 8 == 0 && V > 2 && ignore >= 0 && ignore < V && ls >= 0.f && ls <= 1.f,
+             "x2_mlm_ls_bwd: R=%d Vp=%d V=%d Hd=%d ldd=%ld ignore=%ld", R, Vp, V, Hd, ldd, ignore);
+  GemmNT p{(const bf16_t*)X, (const bf16_t*)E, dl_bf16, bias, nullptr, nullptr, nullptr, R, Vp, Hd, ldx, lde, (int)ldd, 0, 0, 0, 0,
+           g_tune[0] > 0 ? g_tune[0] : 8, DropSpec{0u, 0u, 1.f}, nullptr, nullptr, nullptr, 0, 0,
+           labels, lse, g, stat, nullptr, nullptr, gscale, V, nullptr, nullptr, ignore, ls, w};
+  launch_nt_ce(p, 12, (hipStream_t)stream);
+  return x2_check_launch("x2_mlm_ls_bwd");
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -618,3 +618,120 @@ extern "C" int x2_frame_mean(const float* x, const float* pos, const float* dy, 
   }
   return x2_check_launch("x2_frame_mean");
 }
+
+// ------------------------------------------------------------------------------------ captioning fine-tune (additive to ABI v14)
+// Embedding with explicit position ids (FG-free collate: a [MASK] and the token after it share a position):
+// out[r] = word[ids[r]] + pos[pids[r]] + type0.  ids / pids must index their tables (like the word ids of x2_embed_fwd).
+__global__ __launch_bounds__(256) void embed_fwd_pid_kernel(const long* __restrict__ ids, const long* __restrict__ pids, const float* __restrict__ word,
+                                                            const float* __restrict__ pos, const float* __restrict__ type0, float* __restrict__ out, int D) {
+  const int r = blockIdx.x;
+  const long id = ids[r], l = pids[r];
+  for (int d = threadIdx.x * 4; d < D; d += 1024) {
+    const float4 a = *reinterpret_cast<const float4*>(word + id * D + d), b = *reinterpret_cast<const float4*>(pos + l * D + d),
+                 c = *reinterpret_cast<const float4*>(type0 + d);
+    *reinterpret_cast<float4*>(out + (long)r * D + d) = float4{a.x + b.x + c.x, a.y + b.y + c.y, a.z + b.z + c.z, a.w + b.w + c.w};
+  }
+}
+extern "C" int x2_embed_fwd_pid(const long* ids, const long* pids, const float* word, const float* pos, const float* type0, float* out, int R, int D,
+                                void* stream) {
+  X2_REQUIRE(ids && pids && word && pos && type0 && out && R > 0 && D % 4 == 0, "x2_embed_fwd_pid: R=%d D=%d", R, D);
+  hipLaunchKernelGGL(embed_fwd_pid_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, ids, pids, word, pos, type0, out, D);
+  return x2_check_launch("x2_embed_fwd_pid");
+}
+// per-slot row totals tot[l] = sum of g[r] over r % L == l (the type-0 row's first stage, without a position table to add to)
+__global__ __launch_bounds__(256) void embed_rowsum_kernel(const float* __restrict__ g, float* tot, int R, int L, int D) {
+  const int l = blockIdx.x, d = (blockIdx.y * 256 + threadIdx.x) * 4;
+  if (d >= D) return;
+  float4 t{0.f, 0.f, 0.f, 0.f};
+  for (int r = l; r < R; r += L) {
+    const float4 v = *reinterpret_cast<const float4*>(g + (long)r * D + d);
+    t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
+  }
+  *reinterpret_cast<float4*>(tot + (long)l * D + d) = t;
+}
+// dword[ids[r]] += g[r] ; dpos[pids[r]] += g[r] ; dtype0 += g[r]: both table gradients by the leader-list reducer of x2_embed_bwd
+// (embed_bwd_word_kernel: fixed order, no atomics), the type-0 row through min(L, R) per-slot totals as there.
+extern "C" int x2_embed_bwd_pid(const long* ids, const long* pids, const float* g, float* dword, float* dpos, float* dtype0, int R, int L, int D,
+                                float* scratch, void* stream) {
+  X2_REQUIRE(ids && pids && g && dword && dpos && dtype0 && scratch && R > 0 && L > 0 && D % 4 == 0 && D <= 4096,
+             "x2_embed_bwd_pid: R=%d L=%d D=%d (D <= 4096, scratch of min(L, R) * D floats)", R, L, D);
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(embed_bwd_word_kernel, dim3(R), dim3(1024), 0, st, ids, g, dword, R, D);
+  hipLaunchKernelGGL(embed_bwd_word_kernel, dim3(R), dim3(1024), 0, st, pids, g, dpos, R, D);
+  const int Lp = L < R ? L : R;
+  hipLaunchKernelGGL(embed_rowsum_kernel, dim3(Lp, (D / 4 + 255) / 256), dim3(256), 0, st, g, scratch, R, L, D);
+  hipLaunchKernelGGL(embed_bwd_type_kernel, dim3((D / 4 + 63) / 64), dim3(64), 0, st, scratch, dtype0, Lp, D);
+  return x2_check_launch("x2_embed_bwd_pid");
+}
+
+// out[s][i][j] = (1 - m[s][i][j]) * neg for j < L, 0 in the pad columns L..Lp-1: the 2-D twin of x2_additive_mask (BertModel's extended mask of a
+// [B, L, L] attention mask, xbert get_extended_attention_mask) in the [S][L][Lp] layout x2_attn_fwd_mask2d reads.  One launch.
+__global__ __launch_bounds__(256) void additive_mask2d_kernel(const long* __restrict__ m, float* __restrict__ out, long rows, int L, int Lp, float neg) {
+  const long e = blockIdx.x * 256L + threadIdx.x;
+  if (e >= rows * Lp) return;
+  const long row = e / Lp;
+  const int j = (int)(e % Lp);
+  out[e] = j < L ? (1.0f - (float)m[row * L + j]) * neg : 0.f;
+}
+extern "C" int x2_additive_mask2d(const long* m, float* out, int S, int L, int Lp, float neg, void* stream) {
+  X2_REQUIRE(m && out && S > 0 && L > 0 && Lp >= L, "x2_additive_mask2d: S=%d L=%d Lp=%d", S, L, Lp);
+  const long rows = (long)S * L;
+  hipLaunchKernelGGL(additive_mask2d_kernel, dim3((unsigned)((rows * Lp + 255) / 256)), dim3(256), 0, (hipStream_t)stream, m, out, rows, L, Lp, neg);
+  return x2_check_launch("x2_additive_mask2d");
+}
+
+// Label-smoothed MLM loss, second stage (first stage: x2_mlm_ls_fwd, gemm.hip).  Target distribution of a row with label t (LabelSmoothingLoss of the
+// captioning fine-tune): q[t] = conf = 1 - ls, q[c] = s = ls / (V - 2) elsewhere, q[ignore] = 0, and q = 0 on the whole row when t == ignore.
+//   KL_r = sum_c q log q - s * (sum z - z_t - z_ign) - conf * z_t + sum(q) * lse
+// from the chunk statistics (max, sum exp), the chunk sums of z, z_t and z_ign.  One wave per row.
+__device__ __forceinline__ void ls_consts(int V, float ls, float& conf, float& s, float& qsum, float& qlogq) {
+  conf = 1.f - ls;
+  s = ls / (float)(V - 2);
+  qsum = conf + s * (float)(V - 2);
+  qlogq = (conf > 0.f ? conf * logf(conf) : 0.f) + (s > 0.f ? (float)(V - 2) * s * logf(s) : 0.f);
+}
+__global__ __launch_bounds__(256) void ls_combine_kernel(const float* __restrict__ part, const float* __restrict__ sumz, int chunks,
+                                                         const float* __restrict__ zlab, const float* __restrict__ zign, const long* __restrict__ labels,
+                                                         int R, int V, long ignore, float ls, float* lse, float* kl_row) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (r >= R) return;
+  const float2* pr = reinterpret_cast<const float2*>(part) + (size_t)r * chunks;
+  const float* zr = sumz + (size_t)r * chunks;
+  float mx = -INFINITY;
+  for (int c = lane; c < chunks; c += 64) mx = fmaxf(mx, pr[c].x);
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  float s = 0.f, sz = 0.f;
+  for (int c = lane; c < chunks; c += 64) { const float2 q = pr[c]; s += q.y * __expf(q.x - mx); sz += zr[c]; }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) { s += __shfl_xor(s, o, 64); sz += __shfl_xor(sz, o, 64); }
+  if (lane == 0) {
+    const float l = mx + logf(s);
+    const long lab = labels[r];
+    float conf, sm, qsum, qlogq;
+    ls_consts(V, ls, conf, sm, qsum, qlogq);
+    lse[r] = l;
+    kl_row[r] = (lab >= 0 && lab != ignore) ? qlogq - sm * (sz - zlab[r] - zign[r]) - conf * zlab[r] + qsum * l : 0.f;
+  }
+}
+// loss = sum_r kl_r * w_r / (sum w + 1e-5); out[0] = loss, out[1] = sum w.  One workgroup, fixed order.
+__global__ __launch_bounds__(256) void ls_reduce_kernel(const float* __restrict__ kl_row, const float* __restrict__ w, int R, float* out) {
+  __shared__ float sh[8];
+  float sw = 0.f;
+  for (int r = threadIdx.x; r < R; r += 256) sw += w[r];
+  sw = block_reduce(sw, sh, false);
+  const float inv = 1.f / (sw + 1e-5f);
+  float s = 0.f;
+  for (int r = threadIdx.x; r < R; r += 256) s += kl_row[r] * (w[r] * inv);
+  s = block_reduce(s, sh, false);
+  if (threadIdx.x == 0) { out[0] = s; out[1] = sw; }
+}
+extern "C" int x2_ls_combine(const float* part, const float* sumz, int chunks, const float* zlab, const float* zign, const long* labels, const float* w,
+                             int R, int V, long ignore, float ls, float* lse, float* kl_row, float* out2, void* stream) {
+  X2_REQUIRE(part && sumz && zlab && zign && labels && w && lse && kl_row && out2 && R > 0 && chunks > 0 && V > 2 && ignore >= 0 && ignore < V &&
+             ls >= 0.f && ls <= 1.f, "x2_ls_combine: R=%d chunks=%d V=%d ignore=%ld ls=%g", R, chunks, V, ignore, (double)ls);
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(ls_combine_kernel, dim3((R + 3) / 4), dim3(256), 0, st, part, sumz, chunks, zlab, zign, labels, R, V, ignore, ls, lse, kl_row);
+  hipLaunchKernelGGL(ls_reduce_kernel, dim3(1), dim3(256), 0, st, kl_row, w, R, out2);
+  return x2_check_launch("x2_ls_combine");
+}

@@ -749,6 +749,8 @@ class BertLayersFn(torch.autograd.Function):
     enc: (Bi,T,Dv) fp32 image tokens or None; sequence s attends image kv_idx[s] (several text rows
     may share one image: K/V are projected once per image per layer).
     meta: dict(lo, hi, fusion_at, heads, eps, self_mask [S,Lp] fp32 additive, enc_mask [S,Tp],
+               self_mask2d (optional) [S,L,Lp] fp32 additive per (query, key) - a 3-D text mask (captioning fine-tune), taking the
+               place of self_mask in every layer's self-attention (kernels.attn_fwd_mask2d / attn_bwd_mask2d),
                kv_idx/seq_off/seq_ids int32 or None,
                drop: None or dict(seed, p_hidden, p_attn): training-mode dropout (xbert.py:399, 429, 513), masks are
                regenerated in the backward from (seed, site = 8*layer + {0 self probs, 1 self out, 2 cross probs,
@@ -819,8 +821,12 @@ class BertLayersFn(torch.autograd.Function):
             att = torch.empty(M, Hd, device=dev, dtype=BF16)
             lse = torch.empty(S * H * L, device=dev, dtype=F32)
             dr = BertLayersFn._drop
-            K.attn_fwd(K.view3(qkv, S, L, 0), K.view3(qkv, S, L, Hd), K.view3(qkv, S, L, 2 * Hd), S, S, H, L, L, scale,
-                       K.view3(att, S, L), lse, mask=meta["self_mask"], drop=dr(meta, i, 0))
+            if meta.get("self_mask2d") is not None:
+                K.attn_fwd_mask2d(K.view3(qkv, S, L, 0), K.view3(qkv, S, L, Hd), K.view3(qkv, S, L, 2 * Hd), S, H, L, scale,
+                                  K.view3(att, S, L), lse, meta["self_mask2d"], drop=dr(meta, i, 0))
+            else:
+                K.attn_fwd(K.view3(qkv, S, L, 0), K.view3(qkv, S, L, Hd), K.view3(qkv, S, L, 2 * Hd), S, S, H, L, L, scale,
+                           K.view3(att, S, L), lse, mask=meta["self_mask"], drop=dr(meta, i, 0))
             wo, _ = BANK.linear(p[a + "output.dense.weight"])
             s1 = K.gemm_nt(att, wo, bias=p[a + "output.dense.bias"], resid=h, out_dtype=F32, drop=dr(meta, i, 1))
             h1b, h1, m1, r1 = K.layernorm_fwd(s1, p[a + "output.LayerNorm.weight"], p[a + "output.LayerNorm.bias"], eps, want_f32=True)
@@ -974,9 +980,14 @@ class BertLayersFn(torch.autograd.Function):
             datt = K.gemm_nt(ds1b, woT)
             dqkv = torch.empty_like(qkv)
             delta = torch.empty_like(lse)
-            K.attn_bwd(K.view3(qkv, S, L, 0), K.view3(qkv, S, L, Hd), K.view3(qkv, S, L, 2 * Hd), K.view3(att, S, L), K.view3(datt, S, L),
-                       S, S, H, L, L, scale, lse, delta, K.view3(dqkv, S, L, 0), K.view3(dqkv, S, L, Hd), K.view3(dqkv, S, L, 2 * Hd),
-                       mask=meta["self_mask"], drop=BertLayersFn._drop(meta, i, 0))
+            if meta.get("self_mask2d") is not None:
+                K.attn_bwd_mask2d(K.view3(qkv, S, L, 0), K.view3(qkv, S, L, Hd), K.view3(qkv, S, L, 2 * Hd), K.view3(att, S, L),
+                                  K.view3(datt, S, L), S, H, L, scale, lse, delta, K.view3(dqkv, S, L, 0), K.view3(dqkv, S, L, Hd),
+                                  K.view3(dqkv, S, L, 2 * Hd), meta["self_mask2d"], drop=BertLayersFn._drop(meta, i, 0))
+            else:
+                K.attn_bwd(K.view3(qkv, S, L, 0), K.view3(qkv, S, L, Hd), K.view3(qkv, S, L, 2 * Hd), K.view3(att, S, L), K.view3(datt, S, L),
+                           S, S, H, L, L, scale, lse, delta, K.view3(dqkv, S, L, 0), K.view3(dqkv, S, L, Hd), K.view3(dqkv, S, L, 2 * Hd),
+                           mask=meta["self_mask"], drop=BertLayersFn._drop(meta, i, 0))
             _param_only(po, K.colsum_bf16, dqkv, G["a.qkv_bias"])
             for k3, nm in enumerate(("query", "key", "value")):
                 G.alias("attention.self.%s.bias" % nm, G["a.qkv_bias"][k3 * Hd:(k3 + 1) * Hd])
@@ -1003,16 +1014,21 @@ class BertLayersFn(torch.autograd.Function):
 
 class EmbeddingsFn(torch.autograd.Function):
     """ids (S,L) -> dropout(LayerNorm(word + position + type0)) (S,L,Hd) fp32.  xbert.py:189-216.
-    drop: kernels.dropout_spec(...) triple or kernels.NO_DROP."""
+    drop: kernels.dropout_spec(...) triple or kernels.NO_DROP.
+    pids: optional int64 (S,L) explicit position ids (captioning FG-free collate: repeats allowed); None = position r % L."""
 
     @staticmethod
-    def forward(ctx, ids, eps, drop, word, pos, typ, lnw, lnb):
+    def forward(ctx, ids, eps, drop, word, pos, typ, lnw, lnb, pids=None):
         S, L = ids.shape
         ids = ids.contiguous()
-        e = K.embed_fwd(ids, word.detach(), pos.detach(), typ.detach())
+        if pids is not None:
+            pids = pids.to(torch.int64).expand(S, L).contiguous()
+            e = K.embed_fwd_pid(ids, pids, word.detach(), pos.detach(), typ.detach())
+        else:
+            e = K.embed_fwd(ids, word.detach(), pos.detach(), typ.detach())
         _, y, mean, rstd = K.layernorm_fwd(e, lnw, lnb, eps, want_bf16=False, want_f32=True, drop=drop)
         ctx.save_for_backward(ids, e, mean, rstd, word, pos, typ, lnw)
-        ctx.drop = drop
+        ctx.drop, ctx.pids = drop, pids
         return y.view(S, L, -1)
 
     @staticmethod
@@ -1026,8 +1042,11 @@ class EmbeddingsFn(torch.autograd.Function):
         dword = _TIED_DWORD.pop(_tok(word), None)          # the tied decoder's gradient, if the MLM head left it (TIE_WORD_GRAD)
         if dword is None:
             dword = torch.zeros_like(word)
-        K.embed_bwd(ids, de, dword, dpos, dtyp)
-        return None, None, None, dword, dpos, dtyp, dw, db
+        if ctx.pids is not None:
+            K.embed_bwd_pid(ids, ctx.pids, de, dword, dpos, dtyp)
+        else:
+            K.embed_bwd(ids, de, dword, dpos, dtyp)
+        return None, None, None, dword, dpos, dtyp, dw, db, None
 
 
 # ----------------------------------------------------------------------------- MLM head + loss
@@ -1041,10 +1060,14 @@ class MlmLossFn(torch.autograd.Function):
 
     Fused path (default): the decoder GEMM's epilogue reduces the logits to softmax statistics, the backward recomputes the
     GEMM and writes (softmax - onehot) * g / count straight to bf16 (csrc/gemm.hip, x2_mlm_ce_fwd / _bwd): no [R, Vp] fp32
-    tensor (94 MB at R = 768) is written, saved or read."""
+    tensor (94 MB at R = 768) is written, saved or read.
+
+    smooth: optional (weights fp32 [R], ignore id, label smoothing) - the captioning fine-tune's loss instead of the mean CE: per row the
+    KL divergence from the smoothed target (LabelSmoothingLoss), times weights / (sum(weights) + 1e-5), summed (x2_mlm_ls_fwd / _bwd, the
+    same fused GEMM with its own epilogues; fused path only)."""
 
     @staticmethod
-    def forward(ctx, rows, labels, eps, keep_logits, dw_, db_, lnw, lnb, dec_bias, word):
+    def forward(ctx, rows, labels, eps, keep_logits, dw_, db_, lnw, lnb, dec_bias, word, smooth=None):
         R, Hd = rows.shape
         V = word.shape[0]
         rb = K.cast_bf16(rows.contiguous())
@@ -1057,10 +1080,16 @@ class MlmLossFn(torch.autograd.Function):
         bias_p = BANK.vector(dec_bias, Vp - V) if Vp > V else dec_bias.detach()        # zero-padded to the padded vocabulary
         labels = labels.contiguous().view(-1)
         ctx.fused = FUSED_MLM_CE
+        ctx.smooth = smooth
+        if smooth is not None and not ctx.fused:
+            raise NotImplementedError("the label-smoothed MLM loss has the fused form only (engine.FUSED_MLM_CE)")
         logits = None
         if not ctx.fused or keep_logits or KEEP_MLM_LOGITS:
             logits = K.gemm_nt(tb, Eb, bias=bias_p, out_dtype=F32)
-        if ctx.fused:
+        if smooth is not None:
+            stat, lse = K.mlm_ls_fwd(tb, Eb, bias_p, labels, smooth[0], V, smooth[1], smooth[2])
+            saved = bias_p
+        elif ctx.fused:
             stat, lse = K.mlm_ce_fwd(tb, Eb, bias_p, labels, V)
             saved = bias_p
         else:
@@ -1081,7 +1110,10 @@ class MlmLossFn(torch.autograd.Function):
         dev = rb.device
         Eb, EbT = BANK.vocab(word)
         g1 = g.reshape(1).to(F32).contiguous()
-        if ctx.fused:
+        if ctx.smooth is not None:
+            w, ignore, ls = ctx.smooth
+            dl = K.mlm_ls_bwd(tb, Eb, saved, labels, w, lse, g1, stat, V, ignore, ls)
+        elif ctx.fused:
             dl = K.mlm_ce_bwd(tb, Eb, saved, labels, lse, g1, stat, V)
         else:
             dl = K.ce_bwd(saved, labels, lse, g1, stat, C_valid=V, out_dtype=BF16)
@@ -1104,7 +1136,7 @@ class MlmLossFn(torch.autograd.Function):
         if TIE_WORD_GRAD:
             _TIED_DWORD[_tok(word)] = dword
             dword = None
-        return drows, None, None, None, ddw, dbd, dlnw, dlnb, dbias[:V], dword
+        return drows, None, None, None, ddw, dbd, dlnw, dlnb, dbias[:V], dword, None
 
 
 # ----------------------------------------------------------------------------- small differentiable ops (heads)

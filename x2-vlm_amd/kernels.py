@@ -328,6 +328,35 @@ def attn_bwd(q, k, v, o, do, B, Bkv, H, Lq, Lk, scale, lse, delta, dq, dk, dv, d
     call("x2_attn_bwd", C.byref(a))
 
 
+def _check_mask2d(mask2d, B, L):
+    assert mask2d.dtype == F32 and mask2d.dim() == 3 and mask2d.is_contiguous() and mask2d.shape[:2] == (B, L)
+    assert mask2d.shape[2] % 64 == 0 and mask2d.shape[2] >= L
+
+
+def attn_fwd_mask2d(q, k, v, B, H, L, scale, out, lse, mask2d, drop=NO_DROP, head_dim=64):
+    """Self-attention over L <= 128 tokens with a per-sequence additive mask mask2d [B, L, round_up(L, 64)] fp32 (additive_mask2d) read per
+    (query, key): the captioning fine-tune's tril / FG-free text mask.  q / k / v / out as attn_fwd (view3)."""
+    _check_mask2d(mask2d, B, L)
+    a = _attn_args(q, k, v, B, B, H, L, L, scale, drop=drop, head_dim=head_dim)
+    a.Out, a.o_bs, a.o_rs = out
+    assert lse.dtype == F32 and lse.numel() == B * H * L
+    a.LSE = lse.data_ptr()
+    call("x2_attn_fwd_mask2d", C.byref(a), mask2d.data_ptr(), mask2d.shape[2])
+
+
+def attn_bwd_mask2d(q, k, v, o, do, B, H, L, scale, lse, delta, dq, dk, dv, mask2d, drop=NO_DROP, head_dim=64):
+    """Backward of attn_fwd_mask2d (dQ, then dK / dV; no atomics)."""
+    _check_mask2d(mask2d, B, L)
+    a = _attn_args(q, k, v, B, B, H, L, L, scale, drop=drop, head_dim=head_dim)
+    a.O, a.o_bs, a.o_rs = o
+    a.dO, a.do_bs, a.do_rs = do
+    a.dQ, a.dq_bs, a.dq_rs = dq
+    a.dK, a.dk_bs, a.dk_rs = dk
+    a.dV, a.dv_bs, a.dv_rs = dv
+    a.LSE, a.Delta = lse.data_ptr(), delta.data_ptr()
+    call("x2_attn_bwd_mask2d", C.byref(a), mask2d.data_ptr(), mask2d.shape[2])
+
+
 # ----------------------------------------------------------------------------- row-wise
 
 def layernorm_fwd(x, w, b, eps, *, rows=None, period=0, want_bf16=True, want_f32=False, y_bf16=None, y_f32=None,
@@ -535,6 +564,24 @@ def embed_bwd(ids, g, dword, dpos, dtype):
     call("x2_embed_bwd", ptr(ids), ptr(g), ptr(dword), ptr(dpos), ptr(dtype), R, L, D, ptr(scratch))
 
 
+def embed_fwd_pid(ids, pids, word, pos, type_emb):
+    """embed_fwd with explicit position ids (int64, same shape as ids): out[r] = word[ids[r]] + pos[pids[r]] + type_emb."""
+    assert ids.dtype == torch.int64 and pids.dtype == torch.int64 and ids.shape == pids.shape and ids.is_contiguous() and pids.is_contiguous()
+    R = ids.numel()
+    D = word.shape[1]
+    out = torch.empty(R, D, device=word.device, dtype=F32)
+    call("x2_embed_fwd_pid", ptr(ids), ptr(pids), ptr(word), ptr(pos), ptr(type_emb), ptr(out), R, D)
+    return out
+
+
+def embed_bwd_pid(ids, pids, g, dword, dpos, dtype):
+    R, L = ids.numel(), ids.shape[-1]
+    D = g.shape[-1]
+    assert pids.dtype == torch.int64 and pids.shape == ids.shape and pids.is_contiguous()
+    scratch = workspace(g.device, min(L, R) * D)
+    call("x2_embed_bwd_pid", ptr(ids), ptr(pids), ptr(g), ptr(dword), ptr(dpos), ptr(dtype), R, L, D, ptr(scratch))
+
+
 def gather_rows(src, idx, row_len, want_f32=True, want_bf16=False):
     R = idx.numel()
     assert src.dtype == F32 and src.is_contiguous() and idx.dtype == torch.int32
@@ -627,6 +674,38 @@ def mlm_ce_bwd(x, E, bias, labels, lse, g, stat, V, gscale=1.0):
     return dl
 
 
+def mlm_ls_fwd(x, E, bias, labels, weights, V, ignore, ls):
+    """Label-smoothed, weighted MLM loss of z = x @ E^T + bias without storing z (captioning fine-tune): per row the KL divergence from the
+    smoothed target (q[label] = 1 - ls, ls / (V - 2) elsewhere, 0 at `ignore`; rows labelled `ignore` carry none), times
+    weights / (sum(weights) + 1e-5), summed.  weights fp32 [R].  Returns (stat[2] = (loss, sum of weights), lse[R])."""
+    assert x.dtype == BF16 and E.dtype == BF16 and x.shape[1] == E.shape[1] and bias.dtype == F32 and bias.numel() == E.shape[0]
+    assert labels.dtype == torch.int64 and labels.numel() == x.shape[0] and weights.dtype == F32 and weights.numel() == x.shape[0]
+    R, Hd = x.shape
+    Vp = E.shape[0]
+    dev = x.device
+    part = torch.empty(R, Vp // 64, 2, device=dev, dtype=F32)
+    sumz = torch.empty(R, Vp // 64, device=dev, dtype=F32)
+    small = torch.empty(4 * R + 2, device=dev, dtype=F32)
+    zlab, zign, lse, rows, stat = small[:R], small[R:2 * R], small[2 * R:3 * R], small[3 * R:4 * R], small[4 * R:]
+    with _timed(2.0 * R * Vp * Hd):
+        call("x2_mlm_ls_fwd", ptr(x), ptr(E), ptr(bias), ptr(labels), int(ignore), R, Vp, V, Hd, _rows(x), _rows(E), ptr(part), ptr(sumz),
+             ptr(zlab), ptr(zign))
+    call("x2_ls_combine", ptr(part), ptr(sumz), Vp // 64, ptr(zlab), ptr(zign), ptr(labels), ptr(weights), R, V, int(ignore), float(ls),
+         ptr(lse), ptr(rows), ptr(stat))
+    return stat, lse
+
+
+def mlm_ls_bwd(x, E, bias, labels, weights, lse, g, stat, V, ignore, ls, gscale=1.0):
+    """dlogits bf16 [R, Vp] of mlm_ls_fwd's loss (logits recomputed in the GEMM, never stored)."""
+    R, Hd = x.shape
+    Vp = E.shape[0]
+    dl = torch.empty(R, Vp, device=x.device, dtype=BF16)
+    with _timed(2.0 * R * Vp * Hd, "gemm_nt_recompute"):
+        call("x2_mlm_ls_bwd", ptr(x), ptr(E), ptr(bias), ptr(labels), ptr(weights), ptr(lse), ptr(g), ptr(stat), gscale, float(ls), int(ignore),
+             R, Vp, V, Hd, _rows(x), _rows(E), ptr(dl), Vp)
+    return dl
+
+
 def mask_words(seed, epoch, batch, count):
     """Host mirror of csrc/masking.hip mk_word(): the 32-bit words caption b consumes when none are injected, [batch, count] int64 (CPU)."""
     seed = int(seed) & 0xFFFFFFFF
@@ -678,6 +757,15 @@ def additive_mask(atts, neg):
     S, L = atts.shape
     out = torch.empty(S, round_up(L, 64), device=atts.device, dtype=F32)
     call("x2_additive_mask", ptr(atts), ptr(out), S, L, out.shape[1], float(neg))
+    return out
+
+
+def additive_mask2d(atts, neg):
+    """[S, L, L] 0/1 attention mask (int64) -> [S, L, round_up(L, 64)] fp32 additive mask (1 - m) * neg, pad columns 0."""
+    assert atts.dtype == torch.int64 and atts.dim() == 3 and atts.shape[1] == atts.shape[2] and atts.is_contiguous()
+    S, L = atts.shape[:2]
+    out = torch.empty(S, L, round_up(L, 64), device=atts.device, dtype=F32)
+    call("x2_additive_mask2d", ptr(atts), ptr(out), S, L, out.shape[2], float(neg))
     return out
 
 

@@ -168,3 +168,62 @@ def synth_negatives(seed, batch):
     off_t = r.integers(1, batch, size=(batch,))
     ar = np.arange(batch)
     return [int(x) for x in (ar + off_i) % batch], [int(x) for x in (ar + off_t) % batch]
+
+
+def synth_captioning_batch(seed, batch, max_tokens, max_masks, image_res, vocab_size, fg_free=True, mask_prob=0.25):
+    """Captioning fine-tune batch in the layout of the reference's captioning collate (dataset/captioning_dataset.py), built from its rules:
+    [CLS] caption [SEP], padded with 0; masked positions never the [CLS]; masked_ids padded with PAD_mask = the [CLS] id and weight 0.
+      plain   (fg_free=False): the masked tokens are replaced by [MASK]; L = max_tokens; attention tril over all L; positions 0 .. L-1
+      FG-free (fg_free=True) : a [MASK] is inserted before every masked token and both take that token's position; L = max_tokens +
+                               max_masks; attention tril with every [MASK] slot's column zeroed except its own diagonal entry; the
+                               positions of the padding continue after the last token's
+    Returns a dict of CPU tensors: image, text_ids_masked (B,L), text_atts (B,L,L), position_ids (B,L), masked_pos / masked_ids /
+    masked_weight (B,max_masks), all int64 but image."""
+    r = _rng(seed, "captioning%d" % int(fg_free))
+    big = vocab_size > 2000
+    cls_id, sep_id, mask_id = (101, 102, 103) if big else (1, 2, 3)
+    lo = 1000 if big else 5
+    L = max_tokens + max_masks if fg_free else max_tokens
+    image = r.standard_normal((batch, 3, image_res, image_res), dtype=np.float32)
+    ids_out = np.zeros((batch, L), dtype=np.int64)
+    atts = np.zeros((batch, L, L), dtype=np.int64)
+    pids = np.zeros((batch, L), dtype=np.int64)
+    mpos = np.zeros((batch, max_masks), dtype=np.int64)
+    mids = np.full((batch, max_masks), cls_id, dtype=np.int64)
+    mw = np.zeros((batch, max_masks), dtype=np.int64)
+    for b in range(batch):
+        n = int(r.integers(max(4, max_tokens // 2), max_tokens + 1)) if b else max_tokens
+        tokens = [cls_id] + [int(t) for t in r.integers(lo, vocab_size, size=n - 2)] + [sep_id]
+        n_mask = int(min(max_masks, max(1, round(mask_prob * (n - 1)))))
+        chosen = set(int(p) for p in (r.permutation(n - 1)[:n_mask] + 1))        # never the [CLS]
+        tri = np.tril(np.ones((L, L), dtype=np.int64))
+        if fg_free:
+            seq, pos, slots, targets = [], [], [], []
+            for p, t in enumerate(tokens):
+                if p in chosen:
+                    slots.append(len(seq))
+                    targets.append(t)
+                    seq += [mask_id, t]
+                    pos += [p, p]
+                else:
+                    seq.append(t)
+                    pos.append(p)
+            for s in slots:
+                tri[:, s] = 0
+                tri[s, s] = 1
+            last = len(tokens) - 1
+            pos += list(range(last + 1, last + 1 + (L - len(pos))))
+        else:
+            slots = sorted(chosen)
+            targets = [tokens[p] for p in slots]
+            seq = [mask_id if p in chosen else t for p, t in enumerate(tokens)]
+            pos = list(range(L))
+        k = len(slots)
+        ids_out[b, :len(seq)] = seq
+        atts[b] = tri
+        pids[b] = pos[:L]
+        mpos[b, :k] = slots
+        mids[b, :k] = targets
+        mw[b, :k] = 1
+    out = dict(image=image, text_ids_masked=ids_out, text_atts=atts, position_ids=pids, masked_pos=mpos, masked_ids=mids, masked_weight=mw)
+    return {k_: torch.from_numpy(v) for k_, v in out.items()}

@@ -25,6 +25,14 @@ def _key_mask(atts, neg):
     return _mask_pad((1.0 - atts.float()) * neg, atts.shape[1])
 
 
+def _text_masks(atts):
+    """(self_mask, self_mask2d) of a text attention mask: [S, L] -> additive key mask; [S, L, L] (the captioning collate's tril / FG-free
+    mask, applied per (query, key) as the reference's get_extended_attention_mask does) -> the 2-D additive mask of attn_fwd_mask2d."""
+    if atts.dim() == 3:
+        return None, K.additive_mask2d(atts.to(torch.int64).contiguous(), -10000.0)
+    return _key_mask(atts, -10000.0), None
+
+
 def next_dropout_seed():
     """Per-call dropout seed from the host RNG (torch.manual_seed governs it; no device sync).
     Tests push explicit seeds onto _FIXED_SEEDS."""
@@ -61,12 +69,16 @@ class BertEmbeddings(nn.Module):
         self.eps = config.layer_norm_eps
         self.config = config
 
-    def forward(self, input_ids):
+    def forward(self, input_ids, position_ids=None):
+        """position_ids: None (positions 0 .. L-1) or int (S, L) / (1, L) explicit positions, repeats allowed (xbert.py:189-216)."""
         drop = K.NO_DROP
         if self.training and self.config.hidden_dropout_prob > 0:
             drop = K.dropout_spec(self.config.hidden_dropout_prob, next_dropout_seed(), 1000)
-        return EmbeddingsFn.apply(input_ids, self.eps, drop, self.word_embeddings.weight, self.position_embeddings.weight,
-                                  self.token_type_embeddings.weight, self.LayerNorm.weight, self.LayerNorm.bias)
+        args = (input_ids, self.eps, drop, self.word_embeddings.weight, self.position_embeddings.weight,
+                self.token_type_embeddings.weight, self.LayerNorm.weight, self.LayerNorm.bias)
+        if position_ids is None:
+            return EmbeddingsFn.apply(*args)
+        return EmbeddingsFn.apply(*args, position_ids)
 
 
 class BertSelfAttention(nn.Module):
@@ -127,7 +139,7 @@ class BertEncoder(nn.Module):
 
     def run(self, hidden, text_atts, enc=None, enc_atts=None, mode="multi_modal", kv_idx=None):
         """hidden (S,L,Hd) fp32; enc (Bi,T,Dv) image tokens shared through kv_idx (int (S,), None = identity);
-        enc_atts (S,T) per text row."""
+        enc_atts (S,T) per text row; text_atts (S,L) per key or (S,L,L) per (query, key)."""
         cfg = self.config
         lo, hi = {"text": (0, cfg.fusion_layer), "fusion": (cfg.fusion_layer, cfg.num_hidden_layers),
                   "multi_modal": (0, cfg.num_hidden_layers)}[mode]
@@ -136,8 +148,9 @@ class BertEncoder(nn.Module):
         if self.training and (cfg.hidden_dropout_prob > 0 or cfg.attention_probs_dropout_prob > 0):
             drop = dict(seed=next_dropout_seed(), p_hidden=cfg.hidden_dropout_prob, p_attn=cfg.attention_probs_dropout_prob)
         meta = dict(lo=lo, hi=hi, fusion_at=cfg.fusion_layer, heads=cfg.num_attention_heads, eps=cfg.layer_norm_eps,
-                    self_mask=_key_mask(text_atts, -10000.0), enc_mask=None, kv_idx=None,
+                    self_mask=None, self_mask2d=None, enc_mask=None, kv_idx=None,
                     seq_off=None, seq_ids=None, drop=drop)
+        meta["self_mask"], meta["self_mask2d"] = _text_masks(text_atts)
         cross = enc is not None and hi > cfg.fusion_layer
         if cross:
             Bi = enc.shape[0]
@@ -188,12 +201,10 @@ class BertModel(nn.Module):
         return self.embeddings.word_embeddings
 
     def forward(self, input_ids=None, attention_mask=None, encoder_embeds=None, encoder_hidden_states=None,
-                encoder_attention_mask=None, return_dict=True, mode="multi_modal", kv_idx=None, **unused):
-        """xbert.py:1075-1220 (encoder path: no decoder cache, no head masks)."""
-        for k, v in unused.items():
-            if v not in (None, False):
-                raise NotImplementedError("BertModel.forward(%s=...) is not supported by the HIP path" % k)
-        hidden = self.embeddings(input_ids) if encoder_embeds is None else encoder_embeds
+                encoder_attention_mask=None, return_dict=True, mode="multi_modal", kv_idx=None, position_ids=None, **unused):
+        """xbert.py:1075-1220 (encoder path: no decoder cache, no head masks).  attention_mask (S,L) or (S,L,L)."""
+        _refuse_unused("BertModel", unused)
+        hidden = self.embeddings(input_ids, position_ids) if encoder_embeds is None else encoder_embeds
         S, L = hidden.shape[:2]
         if attention_mask is None:
             attention_mask = torch.ones(S, L, device=hidden.device)
@@ -246,12 +257,26 @@ class BertForMaskedLM(nn.Module):
                                pr.transform.LayerNorm.weight, pr.transform.LayerNorm.bias, pr.bias,
                                self.bert.embeddings.word_embeddings.weight)
 
+    def smoothed_mlm_loss_from_hidden(self, sequence_output, masked_pos, labels, weights, ignore_index, label_smoothing, keep_logits=False):
+        """mlm_loss_from_hidden with the captioning fine-tune's loss: label-smoothed KL per masked slot (ignore_index gets no mass, slots
+        labelled with it no loss), weighted by weights / (sum(weights) + 1e-5) and summed (model_generation.py LabelSmoothingLoss +
+        loss_mask_and_normalize).  Returns (loss, lse, logits or None) as mlm_loss_from_hidden."""
+        B, L, Hd = sequence_output.shape
+        flat = (torch.arange(B, device=masked_pos.device).unsqueeze(1) * L + masked_pos).reshape(-1)
+        rows = ops.gather_rows(sequence_output.reshape(B * L, Hd), flat)
+        pr = self.cls.predictions
+        w = weights.reshape(-1).to(torch.float32).contiguous()
+        return MlmLossFn.apply(rows, labels, self.config.layer_norm_eps, keep_logits, pr.transform.dense.weight, pr.transform.dense.bias,
+                               pr.transform.LayerNorm.weight, pr.transform.LayerNorm.bias, pr.bias,
+                               self.bert.embeddings.word_embeddings.weight, (w, int(ignore_index), float(label_smoothing)))
+
     def forward(self, input_ids=None, attention_mask=None, encoder_hidden_states=None, encoder_attention_mask=None,
-                labels=None, return_dict=True, mode="multi_modal", masked_pos=None, return_logits=False, **unused):
+                labels=None, return_dict=True, mode="multi_modal", masked_pos=None, return_logits=False, position_ids=None, **unused):
+        _refuse_unused("BertForMaskedLM", unused)
         if masked_pos is None:
             raise NotImplementedError("need check!")     # same as the reference, xbert.py:1650-1651
         h = self.bert(input_ids, attention_mask=attention_mask, encoder_hidden_states=encoder_hidden_states,
-                      encoder_attention_mask=encoder_attention_mask, mode=mode).last_hidden_state
+                      encoder_attention_mask=encoder_attention_mask, mode=mode, position_ids=position_ids).last_hidden_state
         lab = labels if labels is not None else torch.full_like(masked_pos, -100)
         loss, _, logits = self.mlm_loss_from_hidden(h, masked_pos, lab, keep_logits=return_logits)
         if logits is not None:
@@ -259,6 +284,13 @@ class BertForMaskedLM(nn.Module):
         if return_logits:
             return logits
         return SimpleNamespace(loss=loss if labels is not None else None, logits=logits)
+
+
+def _refuse_unused(who, unused):
+    """keyword arguments of the reference's signature this path does not implement raise instead of vanishing"""
+    for k, v in unused.items():
+        if v not in (None, False):
+            raise NotImplementedError("%s.forward(%s=...) is not supported by the HIP path" % (who, k))
 
 
 def _bert_init(m, std):
