@@ -3,7 +3,8 @@ seeded inputs.  Inputs that the kernels take in bf16 are rounded to bf16 first, 
 isolates kernel arithmetic (fp32 accumulate) from input quantisation.
 
 Tolerances (relative to each tensor's max-abs): fp32-out kernels 1e-5; bf16-out kernels 6e-3 (one
-bf16 rounding of the output is 2^-9 = 3.9e-3 of the element, plus fp32 summation-order noise)."""
+bf16 rounding of the output is 2^-9 = 3.9e-3 of the element, plus fp32 summation-order noise).
+The head, glue and optimizer kernels at their boundary shapes (float64 references, per-row metrics): tests/test_small_kernels_gpu.py."""
 import importlib
 import os
 import math

@@ -840,20 +840,29 @@ extern "C" int x2_pool_tokens(float* x, const float* w, int B, int P, int D, int
 }
 
 // ---------------------------------------------------------------------------------- rel-pos bias
-// bias[h][i][j] = table[index[i][j]][h] for i,j < N (padded [H][N][ld]); biasT[h][j][i] likewise [H][N][ldT].
+// bias[h][i][j] = table[index[i][j]][h] for i,j < N (padded [H][N][ld]); biasT[h][j][i] likewise [H][N][ldT].  The pad columns
+// N..ld-1 / N..ldT-1 of every row are written as zeros: the buffers arrive uninitialised, and a NaN left in a pad column must
+// not depend on every consumer selecting on key < Lk before it touches the value.
 // indexT (optional) = the transposed index [j][i], built once by the host from the static buffer: with it the transposed
 // copy is written row-contiguously as well (a thread-per-(i,j) scatter into biasT is one 4-byte write per cache line:
 // 57 us per X2VLM-large block).
 __global__ __launch_bounds__(256) void relpos_bias_kernel(const float* __restrict__ table, const long* __restrict__ index,
                                                           const long* __restrict__ indexT, float* bias, float* biasT, int N, int H,
                                                           int ld, int ldT, float scale) {
-  const long total = (long)N * N;
-  long e = blockIdx.x * 256L + threadIdx.x;
-  if (e >= total) return;
-  const int i = (int)(e / N), j = (int)(e % N);
-  const long idx = index[e];
+  const int ldm = biasT && ldT > ld ? ldT : ld;           // one thread per (row i, padded column j)
+  const long e = blockIdx.x * 256L + threadIdx.x;
+  if (e >= (long)N * ldm) return;
+  const int i = (int)(e / ldm), j = (int)(e % ldm);
+  if (j >= N) {
+    for (int h = 0; h < H; ++h) {
+      if (j < ld) bias[((long)h * N + i) * ld + j] = 0.f;
+      if (biasT && j < ldT) biasT[((long)h * N + i) * ldT + j] = 0.f;
+    }
+    return;
+  }
+  const long idx = index[(long)i * N + j];
   if (indexT && biasT) {
-    const long idt = indexT[e];
+    const long idt = indexT[(long)i * N + j];
     for (int h = 0; h < H; ++h) {
       bias[((long)h * N + i) * ld + j] = table[idx * H + h] * scale;
       biasT[((long)h * N + i) * ldT + j] = table[idt * H + h] * scale;
@@ -869,7 +878,8 @@ __global__ __launch_bounds__(256) void relpos_bias_kernel(const float* __restric
 extern "C" int x2_relpos_bias(const float* table, const long* index, const long* indexT, float* bias, float* biasT, int N, int H, int ld,
                               int ldT, float scale, void* stream) {
   X2_REQUIRE(N > 0 && H > 0 && ld >= N && (!biasT || ldT >= N), "x2_relpos_bias: N=%d H=%d ld=%d ldT=%d", N, H, ld, ldT);
-  hipLaunchKernelGGL(relpos_bias_kernel, dim3((int)(((long)N * N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, table, index, indexT,
+  const int ldm = biasT && ldT > ld ? ldT : ld;
+  hipLaunchKernelGGL(relpos_bias_kernel, dim3((int)(((long)N * ldm + 255) / 256)), dim3(256), 0, (hipStream_t)stream, table, index, indexT,
                      bias, biasT, N, H, ld, ldT, scale);
   return x2_check_launch("x2_relpos_bias");
 }

@@ -497,7 +497,7 @@ def relpos_bias(table, index, want_T=True, log2=False):
     N = index.shape[0]
     H = table.shape[1]
     ld = round_up(N, 64)
-    # pad columns stay undefined: the attention kernels select on key < Lk / query < Lq before using a bias value
+    # the kernel writes the pad columns N..ld-1 of both tables as zeros
     bias = torch.empty(H, N, ld, device=table.device, dtype=F32)
     biasT = torch.empty(H, N, ld, device=table.device, dtype=F32) if want_T else None
     call("x2_relpos_bias", ptr(table), ptr(index), ptr(_relpos_index_t(index)) if want_T else None, ptr(bias), ptr(biasT), N, H, ld, ld,
