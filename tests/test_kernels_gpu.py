@@ -4,7 +4,9 @@ isolates kernel arithmetic (fp32 accumulate) from input quantisation.
 
 Tolerances (relative to each tensor's max-abs): fp32-out kernels 1e-5; bf16-out kernels 6e-3 (one
 bf16 rounding of the output is 2^-9 = 3.9e-3 of the element, plus fp32 summation-order noise).
-The head, glue and optimizer kernels at their boundary shapes (float64 references, per-row metrics): tests/test_small_kernels_gpu.py."""
+The head, glue and optimizer kernels at their boundary shapes (float64 references, per-row metrics): tests/test_small_kernels_gpu.py.
+The dropout paths of the attention kernels and of the NT GEMM epilogue against float64 with the mirrored masks (kernels.dropout_keep), dispatch
+branch by dispatch branch and tile family by tile family: tests/test_dropout_kernels_gpu.py."""
 import importlib
 import os
 import math
