@@ -27,7 +27,8 @@ extern "C" {
 const char* x2_last_error(void);
 int x2_abi_version(void);          /* == 14 */
 int x2_device_cus(void);           /* compute units of the current HIP device, 0 if none */
-int x2_tune(int key, int value);   /* kernel-variant knobs for probes/ and tests (0 = automatic); keys listed in csrc/gemm.hip.
+int x2_tune(int key, int value);   /* kernel-variant knobs for probes/ and tests (0 = automatic); keys 0 1 2 3 5 10 12 13 14 15, listed in csrc/gemm.hip,
+                                    * any other key is refused.
                                     * key 12 = compute units every tile plan leaves to RCCL's channel kernels (world > 1);
                                     * key 14 = 1: attention backward as two kernels even where a one-pass kernel applies (3: only the long form 3 off);
                                     * key 15 = NT ping-pong kernel (32x32x16 MFMAs): 0 automatic, 1 never, 3 .. 6 always, at 32 x value rows;

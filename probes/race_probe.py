@@ -42,9 +42,9 @@ def trial(name, setup, n=6):
     print("%-34s mismatching tensors per iteration: %s   worst: %s" % (name, [len(r) for r in res], max((r[0] for r in res if r), default=None)), flush=True)
 
 
-def cfg(side=True, overlap=True, pair=True, hold=False):
+def cfg(side=True, overlap=True, hold=False):
     def f():
-        eng.SIDE.enabled, model.overlap_towers, eng._LayerPairs.enabled = side, overlap, pair
+        eng.SIDE.enabled, model.overlap_towers = side, overlap
         eng.SIDE.hold_forever = hold
     return f
 

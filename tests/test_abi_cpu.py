@@ -75,6 +75,22 @@ def test_attention_backward_form_rules():
     assert h.x2_tune_get(14) == 0
 
 
+def test_tune_keys_kept_and_retired():
+    """x2_tune: the retired A/B keys (6 generic epilogue, 7 no 160x128 tiles, 9 fill threshold, 11 rounds 3-4 rule) are refused like any key
+    that never existed; every kept key holds the value it is given."""
+    h = importlib.import_module("x2-vlm_amd._lib").lib()
+    for k in (6, 7, 9, 11):
+        assert h.x2_tune(k, 1) == -1 and b"x2_tune" in h.x2_last_error(), k
+        assert h.x2_tune_get(k) == -1, k
+    for k in (0, 1, 3, 5, 10, 12, 13, 14, 15):
+        try:
+            assert h.x2_tune(k, 1) == 0, (k, h.x2_last_error())
+            assert h.x2_tune_get(k) == 1, k
+        finally:
+            h.x2_tune(k, 0)
+        assert h.x2_tune_get(k) == 0, k
+
+
 def test_argument_checks_fail_loudly_without_launching():
     lib = importlib.import_module("x2-vlm_amd._lib")
     h = lib.lib()

@@ -1076,39 +1076,35 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(GemmNT p) {
   else run(std::integral_constant<int, RT1>{}, std::false_type{});
 }
 
-// knobs for A/B measurements and for the tests that pin a kernel variant (0 = automatic everywhere)
+// knobs for A/B measurements and for the tests that pin a kernel variant, indexed by key (0 = automatic everywhere)
 //   [0] GROUP_M of the NT tile raster            [1] 0: automatic, 1: 128-column kernels only, 3: always the 256-column kernel
 //   [2] NT ablation bits (4 no epilogue, 16 sc1 stores): -DX2_PROBE builds only, refused by the shipped library
-//   [6] 1: always the generic (run-time flags) NT epilogue
-//   [3] NT tile: 1 = 128x128, 2 = 192x128, 3 = 64x128, 4 = 160x128; 5..8 = rows / 32 of the 256-column kernel        [7] 1: no 160x128 NT tiles
+//   [3] NT tile: 1 = 128x128, 2 = 192x128, 3 = 64x128, 4 = 160x128; 5..8 = rows / 32 of the 256-column kernel
 //   [5] TN: 1 = always 128x128 tiles, 2 = 256x256 tiles whenever the contraction lengths allow
-//   [9] percent of perfect CU fill the 256-column NT kernel's plan must reach to be chosen automatically (0 = 80)
+//   [10] 256-column NT kernel at 160 rows: 0 = three-stage operand ring with pipelined fragment reads (gemm_nt256s3_kernel<V, true>),
+//        2 = three-stage ring, reads at the head of their phase, 1 = the two-stage kernel
 //   [12] compute units every tile plan leaves out (0 = none): with more than one rank RCCL's channel kernels are resident on
 //        some CUs during the backward, and a plan that fills "whole rounds of the 256 CUs" becomes two rounds when a few of
 //        them are taken - graph.SegmentedStep sets it to the channel count it caps RCCL at (X2_RESERVED_CUS)
-static int g_tune[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-//   [10] 256-column NT kernel at 160 rows: 0 = three-stage operand ring with pipelined fragment reads (gemm_nt256s3_kernel<V, true>),
-//        2 = three-stage ring, reads at the head of their phase, 1 = the two-stage kernel
-//   [11] 1: the rounds 3-4 rule for choosing the 256-column kernel (no fp32 + residual launches below K = 2048, no GELU launches)
 //   [13] LayerNorm forward rows per wave (rowwise.hip): 0 automatic, 1 / 2 / 4
 //   [14] 1: attention backward always as the dQ + dK/dV pair (attention.hip: no one-pass kernel at 64 < L <= 208)
 //   [15] ping-pong NT kernel (gemm_nt_pp_kernel): 0 automatic, 1 never, 3 .. 6 always at 96 / 128 / 160 / 192 rows
-static int g_tune_x[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // keys 8.. : [1] = key 9, [4] = key 12
+// every other key is refused
+static int g_tune[16] = {0};
+static bool tune_key(int key) { return key >= 0 && key < 16 && ((0xF42F >> key) & 1); }      // 0 1 2 3 5 10 12 13 14 15
+// percent of perfect CU fill the 256-column NT kernel's plan must reach to be chosen automatically
+static constexpr int NT256_MIN_FILL = 80;
 extern "C" int x2_device_cus(void);
 // compute units of the current device (256 on MI355X), asked once: grid-fill decisions below are made in units of it
 static int x2_cus() {
   static int n = 0;
   if (n <= 0) { n = x2_device_cus(); if (n <= 0) n = 256; }
-  const int left = n - g_tune_x[4];
+  const int left = n - g_tune[12];
   return left >= 16 ? left : 16;
 }
 extern "C" int x2_tune(int key, int value) {
-  if (key >= 9 && key <= 15) {
-    X2_REQUIRE(key != 12 || value >= 0, "x2_tune: reserved compute units = %d", value);
-    g_tune_x[key - 8] = value;
-    return X2_OK;
-  }
-  X2_REQUIRE(key >= 0 && key < 8, "x2_tune: no key %d", key);
+  X2_REQUIRE(tune_key(key), "x2_tune: no key %d", key);
+  X2_REQUIRE(key != 12 || value >= 0, "x2_tune: reserved compute units = %d", value);
 #ifndef X2_PROBE
   X2_REQUIRE(key != 2 || value == 0, "x2_tune: NT ablation bits (key 2, value %d) exist in -DX2_PROBE builds only", value);
 #endif
@@ -1123,9 +1119,7 @@ extern "C" int x2_probe_set_buffer(void* buf) {      // probe builds only: not i
 #endif
 // current value of a knob (bench.py reports every non-default one in its JSON line); -1 for a key that does not exist
 extern "C" int x2_tune_get(int key) {
-  if (key >= 9 && key <= 15) return g_tune_x[key - 8];
-  if (key < 0 || key >= 8) return -1;
-  return g_tune[key];
+  return tune_key(key) ? g_tune[key] : -1;
 }
 
 // 256-column kernel: tile height for this problem.  A launch is a few rounds of one workgroup per CU, each round as long as
@@ -1162,13 +1156,13 @@ static void launch_nt256s3(const GemmNT& p, hipStream_t stream) {
     raised = true;
   }
   const int tiles = ((p.M + 159) / 160) * ((p.N + 255) / 256);
-  if (g_tune_x[2] == 2) hipLaunchKernelGGL((gemm_nt256s3_kernel<V, false>), dim3(tiles), dim3(512), N3_LDS_BYTES, stream, p);
+  if (g_tune[10] == 2) hipLaunchKernelGGL((gemm_nt256s3_kernel<V, false>), dim3(tiles), dim3(512), N3_LDS_BYTES, stream, p);
   else hipLaunchKernelGGL((gemm_nt256s3_kernel<V, true>), dim3(tiles), dim3(512), N3_LDS_BYTES, stream, p);
 }
 template <int V>
 static void launch_nt256_h(const GemmNT& p, int tmw, hipStream_t stream) {
   switch (tmw) {
-    case 5: if (g_tune_x[2] == 1) launch_nt256<5, V>(p, stream); else launch_nt256s3<V>(p, stream); break;
+    case 5: if (g_tune[10] == 1) launch_nt256<5, V>(p, stream); else launch_nt256s3<V>(p, stream); break;
     case 6: launch_nt256<6, V>(p, stream); break;
     case 7: launch_nt256<7, V>(p, stream); break;
     default: launch_nt256<8, V>(p, stream); break;
@@ -1192,8 +1186,8 @@ template <int V>
 static void launch_nt_pp_h(const GemmNT& p, int h, hipStream_t stream) {
   switch (h) {
     case 3: launch_nt_pp<1, 2, V, 3>(p, stream); break;
-    case 4: if (g_tune_x[2] == 1) launch_nt_pp<2, 2, V, 2>(p, stream); else launch_nt_pp<2, 2, V, 3>(p, stream); break;
-    case 5: if (g_tune_x[2] == 1) launch_nt_pp<2, 3, V, 2>(p, stream); else launch_nt_pp<2, 3, V, 3>(p, stream); break;
+    case 4: if (g_tune[10] == 1) launch_nt_pp<2, 2, V, 2>(p, stream); else launch_nt_pp<2, 2, V, 3>(p, stream); break;
+    case 5: if (g_tune[10] == 1) launch_nt_pp<2, 3, V, 2>(p, stream); else launch_nt_pp<2, 3, V, 3>(p, stream); break;
     default: launch_nt_pp<3, 3, V, 2>(p, stream); break;
   }
 }
@@ -1227,8 +1221,7 @@ extern "C" int x2_gemm_nt(const void* A, const void* B, void* C, int M, int N, i
   int var = 4;
   {
     const bool plain = !gamma && !rowscale && !drop_thr16 && !colsum;
-    if (g_tune[6] == 1) var = 4;                                                     // probes / tests: force the generic epilogue
-    else if (act == 1 && !out_f32 && !resid && plain) var = 2;
+    if (act == 1 && !out_f32 && !resid && plain) var = 2;
     else if (act == 2 && !out_f32 && !resid && plain) var = 3;
     else if (act == 0 && !aux && !resid && plain) var = out_f32 ? 1 : 0;
     else if (act == 0 && !aux && resid && out_f32 && !gamma && !rowscale && !colsum) var = 5;
@@ -1244,25 +1237,23 @@ extern "C" int x2_gemm_nt(const void* A, const void* B, void* C, int M, int N, i
   // a small part of the tile - long contractions (K >= 2048: 1.19 vs 1.07 PFLOP/s main loops) or single-output bf16 / fp32
   // epilogues - and its plan fills >= 80 % of the CU rounds; never for the short fp32 + residual launches of the text rows.
   const bool light = var == 0 || var == 1;
-  bool auto256 = (light || K >= 2048) && eff256 * 100.0 >= (g_tune_x[1] > 0 ? g_tune_x[1] : 80) && !(resid && M < 8192);
+  bool auto256 = (light || K >= 2048) && eff256 * 100.0 >= NT256_MIN_FILL && !(resid && M < 8192);
   // Round 5, with the three-stage ring at 160 rows and outputs that are NOT cache-resident (probes/bench_nt_choice.py,
   // profiles/r09k_nt_kernel_choice.txt): the fp32 + residual launches of the long-row towers win on this kernel at any K (vision proj
   // 37.2 -> 28.8 us, X2VLM-large 68.1 -> 58.5, the image-token input gradient of the cross-attentions 41.4 -> 40.1), and so do the
   // GELU launches whose plan fills >= 90 % of its rounds (vision fc1 92.6 -> 88.4, fusion ffn1 57.6 -> 55.1 at 192 rows, X2VLM-large
-  // fc1 199.6 -> 183.7 at 256 rows); the text / fusion rows (M < 8192) with a residual stay where they were.  x2_tune(11, 1): the old rule.
-  if (g_tune_x[3] != 1) {
-    if ((var == 5 || var == 6) && M >= 8192 && eff256 * 100.0 >= (g_tune_x[1] > 0 ? g_tune_x[1] : 80)) auto256 = true;
-    if (var == 2 && eff256 * 100.0 >= 90.0) auto256 = true;
-  }
-  const bool use256 = var != 4 && N % 8 == 0 && (g_tune[1] == 3 || ((g_tune[1] == 0 || g_tune[1] == 4) && g_tune[3] == 0 && auto256));
+  // fc1 199.6 -> 183.7 at 256 rows); the text / fusion rows (M < 8192) with a residual stay where they were.
+  if ((var == 5 || var == 6) && M >= 8192 && eff256 * 100.0 >= NT256_MIN_FILL) auto256 = true;
+  if (var == 2 && eff256 * 100.0 >= 90.0) auto256 = true;
+  const bool use256 = var != 4 && N % 8 == 0 && (g_tune[1] == 3 || (g_tune[1] == 0 && g_tune[3] == 0 && auto256));
   // Ping-pong kernel (gemm_nt_pp_kernel).  x2_tune(15, h), h = 3 .. 6: always, at 32 h rows (probes); 1: never; 0: automatic - the launches the 128-column kernels
   // serve worst: a long contraction (K >= 2048) over few output tiles (the fusion stack's ffn2 forward and ffn1 input gradient, M = 7680 x N = 768: 180 tiles of
   // 128 x 128, 48 serial steps each, 54-61 us), where ONE round of 96- or 128-row x 256-column tiles fills >= 70 % of the CUs: 44-50 us (profiles/r12a_nt_pp_tail.txt).
   // Same sums in the same order as every other NT kernel (bit-identical results: probes/bench_nt_pp.py).  Operands must be addressable through a 2 GB descriptor.
   const bool pp_ok = var != 4 && ((size_t)(M - 1) * lda + K) * 2 < (1ull << 31) && ((size_t)(N - 1) * ldb + K) * 2 < (1ull << 31);
   int pp_h = 0;
-  if (g_tune_x[7] >= 3 && g_tune_x[7] <= 6) pp_h = g_tune_x[7];
-  else if (g_tune_x[7] == 0 && g_tune[1] == 0 && g_tune[3] == 0 && !use256 && K >= 2048 && (var == 0 || var == 1 || var == 5)) {
+  if (g_tune[15] >= 3 && g_tune[15] <= 6) pp_h = g_tune[15];
+  else if (g_tune[15] == 0 && g_tune[1] == 0 && g_tune[3] == 0 && !use256 && K >= 2048 && (var == 0 || var == 1 || var == 5)) {
     const int cus = x2_cus(), tn256 = (N + 255) / 256;
     for (int h = 3; h <= 4 && !pp_h; ++h) {
       const int tiles = ((M + 32 * h - 1) / (32 * h)) * tn256;
@@ -1306,9 +1297,9 @@ extern "C" int x2_gemm_nt(const void* A, const void* B, void* C, int M, int N, i
     const bool use192 = !use64 && (g_tune[3] == 2 || (g_tune[3] == 0 && t128 > slots && t192 <= slots));
     // 160x128 where 192x128 was chosen to save a round and 160-row tiles still fit that one round: the vision N = 768
     // outputs are 79 x 6 = 474 tiles instead of 66 x 6 = 396, i.e. the busiest CU holds 2 x 160 rows instead of 2 x 192
-    // (balanced would be 148): x2_tune(7, 1) switches the rule off
+    // (balanced would be 148)
     const int t160 = ((M + 159) / 160) * ((N + BN - 1) / BN);
-    const bool use160 = g_tune[3] == 4 || (use192 && g_tune[3] == 0 && g_tune[7] != 1 && t160 <= slots);
+    const bool use160 = g_tune[3] == 4 || (use192 && g_tune[3] == 0 && t160 <= slots);
     // fp32-out feature sets (1, 5, 6) store row-contiguously (nt_epilogue_f4: in-step A/B 23.33-23.38 vs 23.42-23.43 ms per base step,
     // profiles/r05i_knob_ab.txt - the 8-columns-per-lane form of these three sets was removed in round 4)
 #define X2_NT_LAUNCH(V, SW)                                                                          \

@@ -12,7 +12,6 @@ Reference behaviour reproduced: beit2.py:125-209, 378-436 (vision), xbert.py:189
 """
 import itertools
 import math
-import os
 import weakref
 
 import torch
@@ -210,9 +209,6 @@ class WeightBank:
 
 
 BANK = WeightBank()
-SPLIT_DECODER_DGRAD = os.environ.get("X2_SPLIT_DECODER_DGRAD", "1") == "1"     # A/B switches (probes/run_ab3.sh)
-FUSED_MLM_CE = os.environ.get("X2_FUSED_MLM_CE", "1") == "1"
-FUSE_DGELU_COLSUM = os.environ.get("X2_FUSE_DGELU_COLSUM", "1") == "1"       # fc1 / intermediate bias gradient from the GELU' GEMM's epilogue
 KEEP_MLM_LOGITS = False     # tests: also materialise the MLM logits (inspection only; the loss still comes from the fused path)
 # Tied decoder / word-embedding gradient in ONE buffer (graph.SegmentedStep switches it on for its passes): the MLM head's
 # backward parks its [V, Hd] weight gradient here instead of handing it to autograd, and the embedding backward - which
@@ -361,8 +357,6 @@ class _LayerPairs:
     (Measured and dropped: un-pairing the LAST two vision layers so that only two weight gradients remain after the critical
     stream has finished block 0 - the split launches cost more than the shorter tail saves: 25.48 -> 25.90 ms per base step.)"""
 
-    enabled = os.environ.get("X2_PAIR_WGRAD", "1") == "1"
-
     def __init__(self):
         self.pending = []
         self.extra = []
@@ -375,7 +369,7 @@ class _LayerPairs:
         finish: K.layerscale_finish items of this layer: run behind its weight-gradient GEMMs (and the stage-2 reductions that
         complete their column sums)."""
         deferred, K.DEFERRED = K.DEFERRED, None
-        if len(tn) > 4 or not self.enabled:
+        if len(tn) > 4:
             self.flush()
             self._launch([(G, tn, deferred)], list(param_only), list(finish))
             return
@@ -432,7 +426,7 @@ class _LayerPairs:
             for fn in WGRAD_QUEUE:
                 if getattr(fn, "params", set()) & later.params:
                     raise RuntimeError("engine.WGRAD_QUEUE: a layer ran twice in one pass; its weight gradients cannot be deferred "
-                                       "(graph.SegmentedStep: defer_tail_wgrad / defer_vision_wgrad)")
+                                       "(graph.SegmentedStep: defer_tail_wgrad, the deferred vision stages)")
             WGRAD_QUEUE.append(later)
             return
         assert not extra, "param_only closures are only collected while WGRAD_QUEUE is set"
@@ -653,11 +647,8 @@ class VisionEncoderFn(torch.autograd.Function):
             _, wqkvT = BANK.linear(p[b + "attn.qkv.weight"])
             if dxb is None:
                 dxb = K.rowscale_cast_colsum(dx, G["_cs2"], rowscale=rs2)
-            if FUSE_DGELU_COLSUM:     # fc1's bias gradient as per-wave partial rows from the GEMM epilogue (no pass over dpre, no atomics)
-                dpre = K.gemm_nt_dgelu_colsum(dxb, w2T, pre, G["mlp.fc1.bias"])
-            else:
-                dpre = K.gemm_nt(dxb, w2T, aux=pre, act=2)
-                K.colsum_bf16(dpre, G["mlp.fc1.bias"])    # two-stage sums: 20 us; fused into the GEMM epilogue with atomics: 30 us
+            # fc1's bias gradient as per-wave partial rows from the GEMM epilogue (no pass over dpre, no atomics)
+            dpre = K.gemm_nt_dgelu_colsum(dxb, w2T, pre, G["mlp.fc1.bias"])
             dh2 = K.gemm_nt(dpre, w1T)            # bf16, like the fp16 grad_input of the reference's O1 linears: half the bytes
             dx1, dx1b = K.layernorm_bwd(dh2, x1, mean2, rstd2, p[b + "norm2.weight"], G["norm2.weight"], G["norm2.bias"], dres=dx,
                                         post=(rs1, G["_cs1"]))
@@ -670,11 +661,11 @@ class VisionEncoderFn(torch.autograd.Function):
             dS_i = torch.empty_like(dS) if WGRAD_QUEUE is not None else dS
             # q / v bias gradient: where the backward is one workgroup per (sequence, head) (form 1) it leaves per-sequence column sums of dQ / dV
             # (round 6: no pass over the [M, 3D] gradient - 58 MB per block); their sum over B joins the layer's stage-2 reductions
-            cs = torch.empty(B, 2, D, device=qkv.device, dtype=F32) if os.environ.get("X2_FUSE_QKV_BIAS_COLSUM", "1") == "1" else None   # (=0: A/B)
+            cs = torch.empty(B, 2, D, device=qkv.device, dtype=F32)
             form = K.attn_bwd(K.view3(qkv, B, T, 0), K.view3(qkv, B, T, D), K.view3(qkv, B, T, 2 * D), K.view3(att, B, T),
                               K.view3(datt, B, T), B, B, H, T, T, scale, lse, delta, K.view3(dqkv, B, T, 0), K.view3(dqkv, B, T, D),
                               K.view3(dqkv, B, T, 2 * D), dS=dS_i, bias=bias, biasT=biasT, bias_log2=True, colsum_ws=cs)
-            fused_cs = cs is not None and form in (1, 3)
+            fused_cs = form in (1, 3)
             if fused_cs:
                 item = (cs, B, 2, D, (G["qkv_bias"][:D], G["qkv_bias"][2 * D:]))
                 if K.DEFERRED is not None:
@@ -915,11 +906,7 @@ class BertLayersFn(torch.autograd.Function):
                                         drop_out=BertLayersFn._drop(meta, i, 4))
             _, woutT = BANK.linear(p[b + "output.dense.weight"])
             _, wiT = BANK.linear(p[b + "intermediate.dense.weight"])
-            if FUSE_DGELU_COLSUM:
-                dpre = K.gemm_nt_dgelu_colsum(ds3b, woutT, pre, G["intermediate.dense.bias"])
-            else:
-                dpre = K.gemm_nt(ds3b, woutT, aux=pre, act=2)
-                K.colsum_bf16(dpre, G["intermediate.dense.bias"])
+            dpre = K.gemm_nt_dgelu_colsum(ds3b, woutT, pre, G["intermediate.dense.bias"])
             dh2 = K.gemm_nt(dpre, wiT, resid=ds3, out_dtype=F32)
             tn += [(ds3b, act, G["output.dense.weight"]), (dpre, h2b, G["intermediate.dense.weight"])]
             if cr is not None:
@@ -1055,16 +1042,16 @@ class MlmLossFn(torch.autograd.Function):
     """rows (R,Hd) fp32 at the masked positions -> mean CE over labels != -100.
     transform dense + GELU + LayerNorm, decoder tied to the word embeddings + bias
     (xbert.py:785-824, 1653-1661).  Returns (loss, lse [R], logits): the per-row log-partition and - only when they were
-    materialised (unfused path, keep_logits, or KEEP_MLM_LOGITS for tests; else None) - the fp32 logits [R, Vp]; neither is
+    materialised (keep_logits, or KEEP_MLM_LOGITS for tests; else None) - the fp32 logits [R, Vp]; neither is
     differentiable.
 
-    Fused path (default): the decoder GEMM's epilogue reduces the logits to softmax statistics, the backward recomputes the
-    GEMM and writes (softmax - onehot) * g / count straight to bf16 (csrc/gemm.hip, x2_mlm_ce_fwd / _bwd): no [R, Vp] fp32
-    tensor (94 MB at R = 768) is written, saved or read.
+    The decoder GEMM's epilogue reduces the logits to softmax statistics, the backward recomputes the GEMM and writes
+    (softmax - onehot) * g / count straight to bf16 (csrc/gemm.hip, x2_mlm_ce_fwd / _bwd): no [R, Vp] fp32 tensor
+    (94 MB at R = 768) is written, saved or read by the loss.
 
     smooth: optional (weights fp32 [R], ignore id, label smoothing) - the captioning fine-tune's loss instead of the mean CE: per row the
     KL divergence from the smoothed target (LabelSmoothingLoss), times weights / (sum(weights) + 1e-5), summed (x2_mlm_ls_fwd / _bwd, the
-    same fused GEMM with its own epilogues; fused path only)."""
+    same fused GEMM with its own epilogues)."""
 
     @staticmethod
     def forward(ctx, rows, labels, eps, keep_logits, dw_, db_, lnw, lnb, dec_bias, word, smooth=None):
@@ -1079,23 +1066,15 @@ class MlmLossFn(torch.autograd.Function):
         Vp = Eb.shape[0]
         bias_p = BANK.vector(dec_bias, Vp - V) if Vp > V else dec_bias.detach()        # zero-padded to the padded vocabulary
         labels = labels.contiguous().view(-1)
-        ctx.fused = FUSED_MLM_CE
         ctx.smooth = smooth
-        if smooth is not None and not ctx.fused:
-            raise NotImplementedError("the label-smoothed MLM loss has the fused form only (engine.FUSED_MLM_CE)")
         logits = None
-        if not ctx.fused or keep_logits or KEEP_MLM_LOGITS:
+        if keep_logits or KEEP_MLM_LOGITS:
             logits = K.gemm_nt(tb, Eb, bias=bias_p, out_dtype=F32)
         if smooth is not None:
             stat, lse = K.mlm_ls_fwd(tb, Eb, bias_p, labels, smooth[0], V, smooth[1], smooth[2])
-            saved = bias_p
-        elif ctx.fused:
-            stat, lse = K.mlm_ce_fwd(tb, Eb, bias_p, labels, V)
-            saved = bias_p
         else:
-            stat, lse = K.ce_fwd(logits, labels, C_valid=V)
-            saved = logits
-        ctx.save_for_backward(rb, t_pre, t_act, mean, rstd, tb, saved, labels, lse, stat, dw_, lnw, word)
+            stat, lse = K.mlm_ce_fwd(tb, Eb, bias_p, labels, V)
+        ctx.save_for_backward(rb, t_pre, t_act, mean, rstd, tb, bias_p, labels, lse, stat, dw_, lnw, word)
         ctx.V = V
         lse_out = lse.clone()
         ctx.mark_non_differentiable(*([lse_out] + ([logits] if logits is not None else [])))
@@ -1103,7 +1082,7 @@ class MlmLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, _glse, _gl):
-        rb, t_pre, t_act, mean, rstd, tb, saved, labels, lse, stat, dw_, lnw, word = ctx.saved_tensors
+        rb, t_pre, t_act, mean, rstd, tb, bias_p, labels, lse, stat, dw_, lnw, word = ctx.saved_tensors
         BANK.note_backward()
         V = ctx.V
         R, Hd = rb.shape
@@ -1112,17 +1091,15 @@ class MlmLossFn(torch.autograd.Function):
         g1 = g.reshape(1).to(F32).contiguous()
         if ctx.smooth is not None:
             w, ignore, ls = ctx.smooth
-            dl = K.mlm_ls_bwd(tb, Eb, saved, labels, w, lse, g1, stat, V, ignore, ls)
-        elif ctx.fused:
-            dl = K.mlm_ce_bwd(tb, Eb, saved, labels, lse, g1, stat, V)
+            dl = K.mlm_ls_bwd(tb, Eb, bias_p, labels, w, lse, g1, stat, V, ignore, ls)
         else:
-            dl = K.ce_bwd(saved, labels, lse, g1, stat, C_valid=V, out_dtype=BF16)
+            dl = K.mlm_ce_bwd(tb, Eb, bias_p, labels, lse, g1, stat, V)
         Vp = dl.shape[1]
         zeros = torch.zeros(Vp + 3 * Hd, device=dev, dtype=F32)          # one fill: decoder-bias gradient + the three head vectors below
         dbias, small = zeros[:Vp], zeros[Vp:]
         K.colsum_bf16(dl, dbias)
         # [R, Hd] from a 30528-long contraction: 36-72 output tiles, so the contraction is split (354 -> ~50 us)
-        dt = K.gemm_nt_splitk(dl, EbT) if SPLIT_DECODER_DGRAD else K.gemm_nt(dl, EbT, out_dtype=F32)
+        dt = K.gemm_nt_splitk(dl, EbT)
         dword = torch.empty_like(word)
         dlnw, dlnb, dbd = small[:Hd], small[Hd:2 * Hd], small[2 * Hd:]
         dact, _ = K.layernorm_bwd(dt, t_act, mean, rstd, lnw, dlnw, dlnb)

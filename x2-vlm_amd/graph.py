@@ -159,12 +159,9 @@ class SegmentedStep:
     _STREAMS = {}
 
     def __init__(self, model, batch, world=1, rank=0, process_group=None, comm=None, warmup=2, enabled=True, verbose=False,
-                 ret_bbox_loss=False, ret_match_loss=True, recast_weights=True, clamp_temp=True, total_loss=None, side_stream=None,
+                 ret_bbox_loss=False, ret_match_loss=True, recast_weights=True, clamp_temp=True, total_loss=None,
                  vision_cuts=None, reduce_grads=True, defer_reduce=False, masking=None):
-        """side_stream: weight-gradient GEMMs of the stream-A segments (tail, vision backward) on engine.SIDE, forked from and
-        joined into stream A inside the segment.  Those segments then replay node by node (~15 us of host time each, still
-        well under the GPU time of a step) but keep the 3 % the side stream is worth on one GPU.  Default: X2_SEG_SIDE or off.
-        reduce_grads=False: no gradient averaging at all (the ITC all-gather stays) - a sub-iteration whose gradients a MixedStep
+        """reduce_grads=False: no gradient averaging at all (the ITC all-gather stays) - a sub-iteration whose gradients a MixedStep
         adds to another step's before ONE reduction; defer_reduce=True: the reduction plan is built but issued by `reduce_all()`
         instead of behind the segments (the accumulating step of a MixedStep)."""
         from . import engine
@@ -188,13 +185,12 @@ class SegmentedStep:
         self.recast_weights, self.clamp_temp = recast_weights, clamp_temp
         self.reduce_grads, self.defer_reduce = reduce_grads, defer_reduce
         self._home = {}                         # id(param) -> the static tensor the captured segments leave its gradient in
-        self.side_stream = (os.environ.get("X2_SEG_SIDE", "0") == "1") if side_stream is None else bool(side_stream)
-        # fusion-layer weight gradients as a segment of their own on stream B (engine.WGRAD_QUEUE); X2_SEG_TAIL_WGRAD=0: in line
+        # fusion-layer weight gradients as a segment of their own on stream B (engine.WGRAD_QUEUE).
         # Not with ret_bbox_loss: predict_bbox runs the fusion layers a SECOND time in the same pass, and a queued weight gradient
         # is only valid with one contribution per parameter - autograd adds the second call's (still empty) arena view to the
         # first's when it receives it, long before the queue fills either; the late TN GEMM then overwrites the sum with one
         # contribution (round 4: the replayed region iteration had lost the other one; the eager path was right).
-        self.defer_tail_wgrad = os.environ.get("X2_SEG_TAIL_WGRAD", "1") == "1" and not ret_bbox_loss
+        self.defer_tail_wgrad = not ret_bbox_loss
         # the tail segment forks a second stream for what hangs off the fusion stack's dependency chain (engine.AUX).  ROCm replays
         # a segment that contains a fork node by node and keeps ONE such replay in flight: the host thread then sits inside
         # hipGraphLaunch for a good part of the step (base 5 ms, region 25 ms per step at 20 enqueued steps).  One GPU: the step stays
@@ -254,8 +250,6 @@ class SegmentedStep:
                 elif 208 < ntok <= 640 and img.dim() == 4:
                     vision_cuts = [depth // 2, depth * 3 // 4]
         self.vcuts = sorted(c for c in vision_cuts if 0 < c < depth)
-        self.defer_vision_wgrad = os.environ.get("X2_SEG_VISION_WGRAD", "1") == "1"
-        self.prefetch_casts = os.environ.get("X2_SEG_PREFETCH_CASTS", "1") == "1" and recast_weights
         self._vq = {}
         self.times = {} if os.environ.get("X2_SEG_TIMES") == "1" else None
         self._held = []
@@ -267,14 +261,14 @@ class SegmentedStep:
         # run twice in a pass) executed on the FIRST object's streams, outside its captures: a race that corrupted memory at
         # random (round 4: `bench.py --config mixed --tiny` died with GPU memory faults, image part first; region first was fine).
         # Step objects never run concurrently, so sharing costs nothing.
-        dev_key = (batch["text_ids"].device.index, os.environ.get("X2_SEG_ONE_STREAM", "0") == "1")
+        # (one stream for everything: 26.56 vs 24.96 ms per base step, profiles/r03f_ab_segments.txt)
+        dev_key = batch["text_ids"].device.index
         st = SegmentedStep._STREAMS.get(dev_key)
         if st is None:
-            a_ = torch.cuda.Stream()
-            st = SegmentedStep._STREAMS[dev_key] = dict(A=a_, B=a_ if dev_key[1] else torch.cuda.Stream(), C=None, G=None)
+            st = SegmentedStep._STREAMS[dev_key] = dict(A=torch.cuda.Stream(), B=torch.cuda.Stream(), C=None, G=None)
         if self.coll and st["C"] is None:
             st["C"], st["G"] = torch.cuda.Stream(), torch.cuda.Stream()
-        self.sA, self.sB = st["A"], st["B"]                      # B == A with X2_SEG_ONE_STREAM=1 (A/B: everything on one stream)
+        self.sA, self.sB = st["A"], st["B"]
         self.sC = st["C"] if self.coll else None                 # gradient all-reduces
         self.sG = st["G"] if self.coll else None                 # ITC all-gathers (see _gather)
         self.t, self.graphs = {}, {}
@@ -296,7 +290,7 @@ class SegmentedStep:
         self._epoch = K.DROP_EPOCH
         cur = torch.cuda.current_stream()
         self.sA.wait_stream(cur)
-        side, tie, hook, rule = engine.SIDE.enabled, engine.TIE_WORD_GRAD, engine.GRAD_READY_HOOK, engine.SIDE.only_from
+        side, tie, hook = engine.SIDE.enabled, engine.TIE_WORD_GRAD, engine.GRAD_READY_HOOK
         engine.GRAD_READY_HOOK = None             # an accelerator's early all-reduce hook must not fire from these passes
         prev_cus = self._reserve()
         try:
@@ -307,7 +301,7 @@ class SegmentedStep:
                 self._capture(verbose)
         finally:
             self._unreserve(prev_cus)
-            engine.SIDE.enabled, engine.TIE_WORD_GRAD, engine.GRAD_READY_HOOK, engine.SIDE.only_from = side, tie, hook, rule
+            engine.SIDE.enabled, engine.TIE_WORD_GRAD, engine.GRAD_READY_HOOK = side, tie, hook
             # the warm-up / capture passes counted stage calls; an accelerator's GradientBuckets reads the counters of the NEXT
             # eager backward_step (a layer that "ran twice" loses its early all-reduce)
             engine.STAGE_CALLS.clear()
@@ -561,10 +555,9 @@ class SegmentedStep:
         if mode == "capture":
             pa, pb = self._pools
         if mode != "replay":
-            # linear segments: weight-gradient GEMMs in line (the other tower fills the CUs) - unless side_stream asks for the
-            # fork / join form on stream A, the capture origin of its segments (engine.SideStream.only_from)
-            eng.SIDE.enabled = self.side_stream
-            eng.SIDE.only_from = self.sA.cuda_stream
+            # linear segments: weight-gradient GEMMs in line (the other tower fills the CUs)
+            # (side stream inside segments: host enqueue 16.6 ms per base step, profiles/r03c_ab_switches.txt)
+            eng.SIDE.enabled = False
             eng.TIE_WORD_GRAD = True
             if self.recast_weights:
                 eng.BANK.invalidate()         # as after an optimizer step: fp32 master weights are re-cast inside the step
@@ -576,7 +569,7 @@ class SegmentedStep:
             self._epoch.add_(1)
         Bs.wait_stream(A)
         self._seg(mode, "T", Bs, self._s_text, pb)
-        if self.prefetch_casts:
+        if self.recast_weights:
             self._seg(mode, "P", Bs, self._s_prefetch, pb)
         self._seg(mode, "V", A, self._s_vision, pa)
         A.wait_stream(Bs)
@@ -597,7 +590,7 @@ class SegmentedStep:
         nstage = len(self.vcuts) + 1
         for ci in range(nstage):
             name = "Vb" if ci == 0 else "Vb%d" % ci
-            defer = self.defer_vision_wgrad and ci < nstage - 1
+            defer = ci < nstage - 1
             if mode != "replay":
                 eng.WGRAD_QUEUE = [] if defer else None
             self._seg(mode, name, A, lambda ci=ci: self._s_vision_bwd(ci), pa)
@@ -776,7 +769,7 @@ class SegmentedStep:
             self._run("replay")
         else:
             eng = self.engine
-            side, tie, hook, rule = eng.SIDE.enabled, eng.TIE_WORD_GRAD, eng.GRAD_READY_HOOK, eng.SIDE.only_from
+            side, tie, hook = eng.SIDE.enabled, eng.TIE_WORD_GRAD, eng.GRAD_READY_HOOK
             eng.GRAD_READY_HOOK = None
             prev_cus = self._reserve()
             try:
@@ -786,7 +779,7 @@ class SegmentedStep:
                         self._reduce_eager_fallback()
             finally:
                 self._unreserve(prev_cus)
-                eng.SIDE.enabled, eng.TIE_WORD_GRAD, eng.GRAD_READY_HOOK, eng.SIDE.only_from = side, tie, hook, rule
+                eng.SIDE.enabled, eng.TIE_WORD_GRAD, eng.GRAD_READY_HOOK = side, tie, hook
                 eng.STAGE_CALLS.clear()
         cur.wait_stream(self.sA)
         return self.t["loss"]
@@ -827,7 +820,6 @@ class TextOnlyStep(SegmentedStep):
             pa, pb = self._pools
         if mode != "replay":
             eng.SIDE.enabled = False
-            eng.SIDE.only_from = A.cuda_stream
             eng.TIE_WORD_GRAD = True              # the embedding lookup of the tied parameter is part of this pass (XT)
             eng.WGRAD_QUEUE = None
             if self.recast_weights:
