@@ -37,6 +37,8 @@ class GradientBuckets:
     the buffer's views (no copy back).  Re-averaging a buffer that already holds an averaged part is exact: the averaged
     part is identical on all ranks, and the mean of identical values is that value."""
 
+    hold = None                    # callable: True while the early path must not be taken (set by _Wrapped's first fused call: has_pending)
+
     def __init__(self, model, world_size, process_group=None, comm=None):
         self.model, self.world, self.pg = model, world_size, process_group
         self.comm = comm           # comm.X2Comm: collectives through the C ABI (x2_comm_*) instead of torch.distributed
@@ -63,6 +65,8 @@ class GradientBuckets:
     def _on_arena(self, flat, key, also_after=None, params=()):
         if engine.STAGE_CALLS.get(key, 0) != 1 or not params or any(p.grad is not None for p in params):
             return
+        if self.hold is not None and self.hold():
+            return                 # a fused call of the wrapper publishes into .grad later in this backward: `.grad + g` would leave the arena
         if self.side is None:
             self._all_reduce(flat)
         else:
@@ -116,12 +120,16 @@ class GradientBuckets:
 
 class _PublishGrads(torch.autograd.Function):
     """Joins the losses of a step whose backward has ALREADY run to autograd: forward hands out the loss values, backward - reached by the
-    caller's accelerator.backward_step(sum of the losses) - publishes the gradients (those of the plain sum of the returned losses,
-    Pretrain.py:67-68 / 98-100) into .grad instead of computing anything."""
+    caller's accelerator.backward_step(c * sum of the losses) - publishes the gradients (c times those of the plain sum of the returned losses,
+    Pretrain.py:67-68 / 98-100; c = iter_perc in run_mixed_iter, :197-223) into .grad instead of computing anything."""
 
     @staticmethod
     def forward(ctx, anchor, owner, pending, values):
         ctx.owner, ctx.pending = owner, pending
+        owner._open = [pd for pd in owner._open if pd["held"] is not None] + [pending]
+        buckets = getattr(owner._acc, "buckets", None)
+        if buckets is not None:
+            buckets.hold = owner.has_pending       # no early all-reduce of a layer arena while these gradients wait to be added to .grad
         return tuple(values.unbind(0))
 
     @staticmethod
@@ -146,9 +154,14 @@ class _Wrapped(torch.nn.Module):
     optimizer.zero_grad() and appear in .grad when backward_step backpropagates the losses.  No autograd graph of the model survives the call, which
     the captures need: an AccumulateGrad node kept alive by a previous iteration's loss tensors stays bound to the stream it was created on.
     Everything else - no-grad / eval calls, text-only calls (image=None), X2_AUTO_CAPTURE=0 - is the plain module call.
-    Limit: the gradients are those of the PLAIN SUM of the returned losses.  A backward with unequal cotangents (a weighted sum, Pretrain.run_mixed_iter's
-    iter_perc) recomputes forward and backward eagerly with the caller's weights - correct, slow, warned about once; accelerator.mixed_step is the
-    fast form of that iteration."""
+    Limit: the gradients computed with the call are those of the PLAIN SUM of the returned losses.  A backward of c * (that sum) - Pretrain.run_mixed_iter
+    multiplies every part by its iter_perc - reads c (one scalar, one host sync) and publishes c * gradients, scaled in place.  A backward with
+    unequal cotangents, or one that leaves a loss out (regions_use_bbox_only), recomputes forward and backward eagerly with the caller's weights -
+    correct, slow, warned about once; its gradients are averaged over the ranks by backward_step.  accelerator.mixed_step is the fast form of that
+    iteration.  Several calls may be pending at once (image + region parts), and calls published without a zero_grad between them accumulate."""
+
+    _local = False                  # this rank's own (not yet averaged) gradients were produced since the last averaging: backward_step finishes the buckets
+    _open = ()                      # fused calls whose gradients wait for the caller's backward
 
     def __init__(self, module, accelerator=None):
         super().__init__()
@@ -171,6 +184,7 @@ class _Wrapped(torch.nn.Module):
               and text_ids_masked is not None and all(torch.is_tensor(v) and v.is_cuda for v in tensors.values()))
         if not ok:
             self.last_mode = "eager"
+            self._local = self._local or torch.is_grad_enabled()
             return call()
         sig = (tuple((k, tuple(v.shape), v.dtype) for k, v in tensors.items()), bool(ret_bbox_loss), bool(ret_match_loss))
         step = self._steps.get(sig)
@@ -215,6 +229,10 @@ class _Wrapped(torch.nn.Module):
         outs = _PublishGrads.apply(anchor, self, dict(held=held, call=call, step=step), values)
         return dict(zip(keys, outs))
 
+    def has_pending(self):
+        """True while a fused call's gradients wait for their backward: whatever else that backward leaves in .grad gets them added."""
+        return any(pd["held"] is not None for pd in self._open)
+
     def _publish(self, pending, cots):
         held, call, step = pending["held"], pending["call"], pending["step"]
         if held is None:
@@ -224,13 +242,21 @@ class _Wrapped(torch.nn.Module):
             step._busy = False
         live = [c for c in cots if c is not None]
         same = len(live) == len(cots) and all(c.data_ptr() == live[0].data_ptr() or bool(torch.equal(c, live[0])) for c in live[1:])
-        if same and os.environ.get("X2_CHECK_COTANGENT", "0") == "1":
-            same = float(live[0]) == 1.0        # host sync: off by default (Pretrain.py backpropagates the plain sum)
         if same:
+            # c * (sum of the losses): c = 1 in run_image_iter / run_region_iter, iter_perc in run_mixed_iter (Pretrain.py:197, 206, 217-223).  One
+            # scalar read (a host sync) where the reference's loop synchronises anyway (loss[...].item(), float(clip_grad_norm) right after)
+            c = float(live[0])
+            if c != 1.0:
+                # in place: the optimizer reads a step's static gradient tensors by identity, and its next replay rewrites them
+                uniq = list({g.data_ptr(): g for _, g in held}.values())
+                with torch.no_grad():
+                    torch._foreach_mul_(uniq, c)
             for p, g in held:
                 p.grad = g if p.grad is None or p.grad is g else p.grad + g      # a second forward of the iteration accumulates (Pretrain.py:197, 247)
             return
-        # a weighted sum: the gradients computed with the forward do not apply - one eager forward + backward with the caller's weights
+        # unequal weights, or a loss left out of the sum: the gradients computed with the forward do not apply - one eager forward + backward with
+        # the caller's weights.  Its gradients are this rank's own: backward_step averages them (self._local)
+        self._local = True
         if not self._warned:
             print("x2-vlm_amd: backward with unequal loss weights through an auto-captured model call - recomputing eagerly (slow). "
                   "accelerator.mixed_step / segmented_step(total_loss=...) are the fast forms of a weighted iteration.", flush=True)
@@ -322,8 +348,13 @@ class RocmDDPAccelerator(Accelerator):
     def backward_step(self, loss, optimizer=None):
         loss.backward()
         wrapped = getattr(self, "ddp_model", None)
-        if wrapped is not None and wrapped.last_mode != "eager":
-            return                               # a fused model call (_Wrapped): forward, backward and the gradient averaging ran inside it
+        if wrapped is not None and wrapped.last_mode != "eager" and not wrapped._local:
+            return                               # fused model calls only (_Wrapped): forward, backward and the gradient averaging ran inside them
+        # this rank's own gradients are in .grad: an eager call anywhere in the iteration (the text part of run_mixed_iter), or a fused call whose
+        # backward was recomputed with the caller's weights.  Published fused gradients in the same .grad are averaged already and identical on
+        # every rank: averaging them again leaves them as they are (GradientBuckets)
+        if wrapped is not None:
+            wrapped._local = False
         if self.buckets is not None:
             self.buckets.finish()
 
