@@ -301,6 +301,24 @@ int x2_frame_mean(const float* x, const float* pos, const float* dy, float* out,
 int x2_gelu_f32(const float* x, const float* dy, float* out, long n, void* stream);               /* nn.GELU, xvlm.py:167 */
 int x2_colsum_f32(const float* x, float* out, int M, int N, void* stream);
 
+/* ---- captioning inference (csrc/decode.hip), additive to ABI v14: one decode step of models/model_generation.py:139-328 ----
+ * Self-attention of a step's n_new tokens per row over a per-row K/V cache.  qkv [S * n_new][qkv_ld >= 3 * Hd] bf16 (Hd = 64 * H), the
+ * fused projection rows; cache [S][Lmax][2 * Hd] bf16 of this layer (K then V), indexed by ABSOLUTE position; hist = positions already
+ * cached, the same for every row.  Writes the new tokens' K/V to cache slots hist .. hist + n_new - 1 and out [S * n_new][out_ld] bf16,
+ * query j attending positions 0 .. hist + j (the tril mask sliced as attention_mask[:, start_pos:next_pos+1, :next_pos+1]).
+ * n_new <= 16, hist + n_new <= Lmax <= 128, Lmax % 8 == 0.  One workgroup owns a (row, head): no query reads another's fresh K/V. */
+int x2_attn_decode(const void* qkv, int qkv_ld, void* cache, void* out, int out_ld, int S, int H, int n_new, int hist, int Lmax, float scale,
+                   void* stream);
+/* dst[l][s][0:hist] = src[l][parent[s]][0:hist] over caches [layers][S][Lmax][row_elems] bf16, one launch for all layers (select_beam_items
+ * and, with parent[s] = s / K, first_expand).  dst beyond hist is left alone; src and dst must not overlap (src == dst is refused). */
+int x2_beam_gather(const void* src, void* dst, const int* parent, int layers, int S, int Lmax, int row_elems, int hist, void* stream);
+/* per row of fp32 logits [S][ldv] (V valid columns, the rest never read): log_softmax; -10000 ADDED to every token seq[i + n - 1] with
+ * seq[i .. i+n-2] equal to the row's last n - 1 ids (seq [S][Lseq] int32, seq_len ids so far, n = ngram; none when seq_len < n, seq NULL or
+ * n == 0: get_dup_ngram_candidates with an empty forbid_ignore_set); column eos_id SET to -10000 when forbid_eos; then the K <= 8 largest
+ * values and their columns, largest first, lowest column first among equal values.  logs (or NULL): the [S][V] penalised log-scores. */
+int x2_logprob_topk(const float* logits, int ldv, int V, int S, const int* seq, int Lseq, int seq_len, int ngram, int eos_id, int forbid_eos,
+                    int K, float* out_vals, int* out_ids, float* logs, void* stream);
+
 /* ---- optimizer (csrc/optim.hip) -- "next" row of the scope table ------------------------------------------
  * optim.py:26-104 (transformers==4.12.5 AdamW, eps 1e-8, betas (0.9,0.98), correct_bias) and the global-norm clip of
  * accelerators/apex_ddp_accelerator.py:99-102, as two multi-tensor launches.  table: ntensors records

@@ -85,6 +85,10 @@ _SIGS = {
     "x2_mlm_ls_fwd": [P, P, P, P, L, I, I, I, I, I, I, P, P, P, P, P],
     "x2_ls_combine": [P, P, I, P, P, P, P, I, I, L, F, P, P, P, P],
     "x2_mlm_ls_bwd": [P, P, P, P, P, P, P, P, F, F, L, I, I, I, I, I, I, P, L, P],
+    # captioning inference (additive to ABI v14)
+    "x2_attn_decode": [P, I, P, P, I, I, I, I, I, I, F, P],
+    "x2_beam_gather": [P, P, P, I, I, I, I, I, P],
+    "x2_logprob_topk": [P, I, I, I, P, I, I, I, I, I, I, P, P, P, P],
 }
 # communicator entry points (csrc/comm.hip): explicit stream / event arguments, bound without the implicit stream of call()
 _COMM_SIGS = {

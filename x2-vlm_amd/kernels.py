@@ -849,3 +849,45 @@ def gelu_f32(x, dy=None):
 
 def colsum_f32(x, out):
     call("x2_colsum_f32", ptr(x), ptr(out), x.shape[0], x.shape[1])
+
+
+# ----------------------------------------------------------------------------- captioning inference (csrc/decode.hip)
+
+def attn_decode(qkv, cache, S, H, n_new, hist, scale, out=None):
+    """Self-attention of a decode step over the per-row K/V cache of one layer.  qkv [S * n_new, 3 * Hd] bf16 (gemm_nt's fused rows), cache
+    [S, Lmax, 2 * Hd] bf16: the new tokens' K/V are written to positions hist .. hist + n_new - 1 and query j attends positions 0 .. hist + j.
+    -> out [S * n_new, Hd] bf16."""
+    Hd = 64 * H
+    assert qkv.dtype == BF16 and qkv.dim() == 2 and qkv.shape == (S * n_new, 3 * Hd) and qkv.stride(1) == 1
+    assert cache.dtype == BF16 and cache.dim() == 3 and cache.is_contiguous() and cache.shape[0] == S and cache.shape[2] == 2 * Hd
+    if out is None:
+        out = torch.empty(S * n_new, Hd, device=qkv.device, dtype=BF16)
+    assert out.dtype == BF16 and out.shape == (S * n_new, Hd) and out.stride(1) == 1
+    call("x2_attn_decode", ptr(qkv), _rows(qkv), ptr(cache), ptr(out), _rows(out), S, H, n_new, hist, cache.shape[1], scale)
+    return out
+
+
+def beam_gather(src, dst, parent, hist):
+    """dst[l, s, :hist] = src[l, parent[s], :hist] for caches [layers, S, Lmax, W] bf16 (two different buffers); parent int32 [S]."""
+    assert src.dtype == BF16 and dst.dtype == BF16 and src.dim() == 4 and src.shape == dst.shape and src.is_contiguous() and dst.is_contiguous()
+    NL, S, Lmax, W = src.shape
+    assert parent.dtype == torch.int32 and parent.numel() == S and parent.is_contiguous()
+    call("x2_beam_gather", ptr(src), ptr(dst), ptr(parent), NL, S, Lmax, W, hist)
+
+
+def logprob_topk(logits, V, k, *, seq=None, seq_len=0, ngram=0, eos_id=0, forbid_eos=False, want_logs=False):
+    """Per row of fp32 logits [S, ldv] (V valid columns): log_softmax, -10000 added to every token completing a repeated `ngram`-gram of the
+    row's ids so far (seq int32 [S, Lseq], seq_len of them), column eos_id set to -10000 when forbid_eos, then the k largest values and
+    their columns (largest first, lowest column first among equals).  -> (vals fp32 [S, k], ids int32 [S, k], logs fp32 [S, V] or None)."""
+    assert logits.dtype == F32 and logits.dim() == 2 and logits.stride(1) == 1
+    S = logits.shape[0]
+    Lseq = 0
+    if seq is not None:
+        assert seq.dtype == torch.int32 and seq.dim() == 2 and seq.shape[0] == S and seq.is_contiguous()
+        Lseq = seq.shape[1]
+    vals = torch.empty(S, k, device=logits.device, dtype=F32)
+    ids = torch.empty(S, k, device=logits.device, dtype=torch.int32)
+    logs = torch.empty(S, V, device=logits.device, dtype=F32) if want_logs else None
+    call("x2_logprob_topk", ptr(logits), _rows(logits), V, S, ptr(seq), Lseq, seq_len, ngram, eos_id, 1 if forbid_eos else 0, k, ptr(vals),
+         ptr(ids), ptr(logs))
+    return vals, ids, logs
