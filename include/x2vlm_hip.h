@@ -319,6 +319,25 @@ int x2_beam_gather(const void* src, void* dst, const int* parent, int layers, in
 int x2_logprob_topk(const float* logits, int ldv, int V, int S, const int* seq, int Lseq, int seq_len, int ngram, int eos_id, int forbid_eos,
                     int K, float* out_vals, int* out_ids, float* logs, void* stream);
 
+/* ---- VQA inference: additive to ABI v14 (csrc/vqa.hip) - XVLMForVQA.rank_answer, models/model_generation.py:562-619.  No existing signature or
+ * struct changes, x2_abi_version() stays 14.  Both selections order by value descending, the LOWER index first among equal values.
+ *   x2_answer_topk : per question row of fp32 first-step logits [B][ldv] (V valid columns, the rest never read):
+ *       logp[c] = z[first_tok[c]] - logsumexp(z) for the Na candidate answers (first_tok int32 [Na], values in [0, V) - a precondition; a value
+ *       outside is not dereferenced and scores -inf), the k largest as vals [B][k] (LOG-probabilities) and their candidate indices ids [B][k].
+ *       Refused without a launch: k outside 1..min(Na, 256), Na outside 1..65536.
+ *   x2_vqa_candidates : rows s = b * k + j of the second decoder pass from answer_ids / answer_atts int64 [Na][La] and ids [B][k]:
+ *       input_ids [S][La]; labels [S][La-1] = the next token, -100 where it is pad_token_id; kv_idx [S] = s / k;
+ *       mask2d [S][La][mask2d_ld] = (1 - tril[i][j] * atts[s][j]) * -10000 for j < La, 0 for La <= j < mask2d_ld (= La rounded up to 64): the
+ *       layout x2_attn_fwd_mask2d reads.  2 <= La <= 128.  An id outside [0, Na) yields an all-padding row.
+ *   x2_vqa_rerank : loss_rows [S][T] (T = La - 1 <= 127, x2_ce_combine's loss_row: 0 on ignored rows), vals / ids of the first stage:
+ *       scores[b][j] = vals[b][j] - (sum of loss_rows[b * k + j][0..T-1], added in index order); softmax over the k <= 256 scores of a question;
+ *       topk_probs [B][k] and topk_ids [B][k] (ids gathered) sorted by score, scores [B][k] unsorted. */
+int x2_answer_topk(const float* logits, int ldv, int V, int B, const int* first_tok, int Na, int K, float* out_vals, int* out_ids, void* stream);
+int x2_vqa_candidates(const long* answer_ids, const long* answer_atts, const int* ids, int Na, int La, int B, int K, long pad_token_id,
+                      long* input_ids, long* labels, int* kv_idx, float* mask2d, int mask2d_ld, void* stream);
+int x2_vqa_rerank(const float* loss_rows, int T, const float* vals, const int* ids, int B, int K, float* topk_probs, int* topk_ids, float* scores,
+                  void* stream);
+
 /* ---- optimizer (csrc/optim.hip) -- "next" row of the scope table ------------------------------------------
  * optim.py:26-104 (transformers==4.12.5 AdamW, eps 1e-8, betas (0.9,0.98), correct_bias) and the global-norm clip of
  * accelerators/apex_ddp_accelerator.py:99-102, as two multi-tensor launches.  table: ntensors records

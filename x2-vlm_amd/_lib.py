@@ -89,6 +89,10 @@ _SIGS = {
     "x2_attn_decode": [P, I, P, P, I, I, I, I, I, I, F, P],
     "x2_beam_gather": [P, P, P, I, I, I, I, I, P],
     "x2_logprob_topk": [P, I, I, I, P, I, I, I, I, I, I, P, P, P, P],
+    # VQA inference (additive to ABI v14)
+    "x2_answer_topk": [P, I, I, I, P, I, I, P, P, P],
+    "x2_vqa_candidates": [P, P, P, I, I, I, I, L, P, P, P, P, I, P],
+    "x2_vqa_rerank": [P, I, P, P, I, I, P, P, P, P],
 }
 # communicator entry points (csrc/comm.hip): explicit stream / event arguments, bound without the implicit stream of call()
 _COMM_SIGS = {

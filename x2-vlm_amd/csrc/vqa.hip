@@ -1,0 +1,179 @@
+// VQA inference (XVLMForVQA.rank_answer, models/model_generation.py:562-619): the three kernels around the two decoder passes.
+//   x2_answer_topk     log-softmax of the first-step logits, gathered at every candidate answer's first token, k best candidates
+//   x2_vqa_candidates  ids, next-token labels, K/V row map and the additive causal x padding mask of the B * k candidate rows
+//   x2_vqa_rerank      score = first-token log-probability - sum of the per-token losses, softmax over a question's k scores, sorted
+// Order rule of both selections: larger value first, the lower index (candidate / slot) first among equal values - a total order, so
+// the result does not depend on how the work is split.  No atomics: every output element has one writer.  The work is tiny (k <= 256
+// per question); what these kernels save is launches, the per-question host loop and the [B * k, La, La] 0/1 mask, so they are plain
+// VALU code with one workgroup per question (candidates: per row).
+#include "x2_common.h"
+#include <math.h>
+
+#define VQ_THREADS 256
+#define VQ_MAXK 256
+#define VQ_MAXNA 65536
+#define VQ_MAXLA 128
+#define VQ_CACHE 8192          // candidates whose log-probability is kept in LDS between the selection rounds (the rest are recomputed)
+static_assert(VQ_THREADS == 256 && VQ_MAXK <= VQ_THREADS, "four waves per workgroup, one thread per selected slot");
+
+__device__ __forceinline__ bool vq_better(float av, int ac, float bv, int bc) { return av > bv || (av == bv && ac < bc); }
+
+// max over the workgroup (four waves); red: 4 floats of LDS, reusable after the call
+__device__ __forceinline__ float vq_block_max(float v, float* red) {
+  v = wave_max(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  return v;
+}
+__device__ __forceinline__ float vq_block_sum(float v, float* red) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  return v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- first stage
+// One workgroup per question row.  logp[c] = (z[first_tok[c]] - max) - log(sum exp(z - max)) over the V valid columns (x2_logprob_topk's
+// arithmetic); a first token outside [0, V) - excluded by the caller - is never dereferenced and scores -inf.  Round r picks the best
+// candidate that comes strictly after round r - 1's winner in the order (value descending, index ascending).
+__global__ __launch_bounds__(VQ_THREADS) void answer_topk_kernel(const float* __restrict__ logits, int ldv, int V, const int* __restrict__ first_tok,
+                                                                 int Na, int K, float* __restrict__ out_vals, int* __restrict__ out_ids) {
+  __shared__ float sLp[VQ_CACHE];
+  __shared__ float sRedF[VQ_THREADS / 64];
+  __shared__ int sRedC[VQ_THREADS / 64];
+  const int row = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const float* x = logits + (size_t)row * ldv;
+  float m = -INFINITY;
+  for (int c = tid; c < V; c += VQ_THREADS) m = fmaxf(m, x[c]);
+  m = vq_block_max(m, sRedF);
+  float sum = 0.f;
+  for (int c = tid; c < V; c += VQ_THREADS) sum += expf(x[c] - m);
+  const float lsum = logf(vq_block_sum(sum, sRedF));
+  auto logp = [&](int c) -> float {
+    const int t = first_tok[c];
+    return (unsigned)t < (unsigned)V ? (x[t] - m) - lsum : -INFINITY;
+  };
+  for (int c = tid; c < Na && c < VQ_CACHE; c += VQ_THREADS) sLp[c] = logp(c);
+  __syncthreads();
+  float pv = INFINITY;
+  int pc = -1;                                                            // the previous winner: everything is after (+inf, -1)
+  for (int r = 0; r < K; ++r) {
+    float bv = -INFINITY;
+    int bc = 0x7fffffff;
+    for (int c = tid; c < Na; c += VQ_THREADS) {                          // ascending c: an equal later value never displaces an earlier one
+      const float v = c < VQ_CACHE ? sLp[c] : logp(c);
+      if (vq_better(pv, pc, v, c) && vq_better(v, c, bv, bc)) { bv = v; bc = c; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oc = __shfl_xor(bc, o, 64);
+      if (vq_better(ov, oc, bv, bc)) { bv = ov; bc = oc; }
+    }
+    if (lane == 0) { sRedF[wave] = bv; sRedC[wave] = bc; }
+    __syncthreads();
+    bv = sRedF[0]; bc = sRedC[0];
+#pragma unroll
+    for (int w = 1; w < VQ_THREADS / 64; ++w)
+      if (vq_better(sRedF[w], sRedC[w], bv, bc)) { bv = sRedF[w]; bc = sRedC[w]; }
+    __syncthreads();
+    if (tid == 0) { out_vals[(size_t)row * K + r] = bv; out_ids[(size_t)row * K + r] = bc; }
+    pv = bv; pc = bc;
+  }
+}
+
+extern "C" int x2_answer_topk(const float* logits, int ldv, int V, int B, const int* first_tok, int Na, int K, float* out_vals, int* out_ids,
+                              void* stream) {
+  X2_REQUIRE(logits && first_tok && out_vals && out_ids, "x2_answer_topk: null tensor");
+  X2_REQUIRE(B > 0 && V > 0 && ldv >= V, "x2_answer_topk: B=%d V=%d ldv=%d", B, V, ldv);
+  X2_REQUIRE(Na >= 1 && Na <= VQ_MAXNA, "x2_answer_topk: Na=%d must be in 1..%d", Na, VQ_MAXNA);
+  X2_REQUIRE(K >= 1 && K <= VQ_MAXK && K <= Na, "x2_answer_topk: k=%d must be in 1..min(Na=%d, %d)", K, Na, VQ_MAXK);
+  hipLaunchKernelGGL(answer_topk_kernel, dim3(B), dim3(VQ_THREADS), 0, (hipStream_t)stream, logits, ldv, V, first_tok, Na, K, out_vals, out_ids);
+  return x2_check_launch("x2_answer_topk");
+}
+
+// ---------------------------------------------------------------------------------------------------------------- candidate rows
+// One workgroup per candidate row s = b * k + j, a = ids[s] its answer.  An id outside [0, Na) (the first stage never returns one for
+// finite logits) reads no answer: the row becomes all padding (labels -100, every key masked).
+__global__ __launch_bounds__(VQ_THREADS) void vqa_candidates_kernel(const long* __restrict__ answer_ids, const long* __restrict__ answer_atts,
+                                                                    const int* __restrict__ ids, int Na, int La, int Lp, int K, long pad_id,
+                                                                    long* __restrict__ input_ids, long* __restrict__ labels,
+                                                                    int* __restrict__ kv_idx, float* __restrict__ mask2d) {
+  __shared__ float sAtt[VQ_MAXLA];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const int a = ids[s];
+  const bool ok = (unsigned)a < (unsigned)Na;
+  const long* src = answer_ids + (size_t)(ok ? a : 0) * La;
+  const long* att = answer_atts + (size_t)(ok ? a : 0) * La;
+  for (int t = tid; t < La; t += VQ_THREADS) {
+    input_ids[(size_t)s * La + t] = ok ? src[t] : pad_id;
+    sAtt[t] = ok ? (float)att[t] : 0.f;
+    if (t + 1 < La) {
+      const long nxt = ok ? src[t + 1] : pad_id;
+      labels[(size_t)s * (La - 1) + t] = nxt == pad_id ? -100L : nxt;
+    }
+  }
+  if (tid == 0) kv_idx[s] = s / K;
+  __syncthreads();
+  float* out = mask2d + (size_t)s * La * Lp;
+  for (int e = tid; e < La * Lp; e += VQ_THREADS) {
+    const int i = e / Lp, j = e - i * Lp;
+    out[e] = j < La ? (1.0f - (j <= i ? sAtt[j] : 0.f)) * -10000.0f : 0.f;
+  }
+}
+
+extern "C" int x2_vqa_candidates(const long* answer_ids, const long* answer_atts, const int* ids, int Na, int La, int B, int K, long pad_token_id,
+                                 long* input_ids, long* labels, int* kv_idx, float* mask2d, int mask2d_ld, void* stream) {
+  X2_REQUIRE(answer_ids && answer_atts && ids && input_ids && labels && kv_idx && mask2d, "x2_vqa_candidates: null tensor");
+  X2_REQUIRE(Na >= 1 && B >= 1 && K >= 1 && (long)B * K < (1L << 31), "x2_vqa_candidates: Na=%d B=%d k=%d", Na, B, K);
+  X2_REQUIRE(La >= 2 && La <= VQ_MAXLA, "x2_vqa_candidates: La=%d must be in 2..%d (the 2-D masked attention's limit)", La, VQ_MAXLA);
+  X2_REQUIRE(mask2d_ld >= La && mask2d_ld % 64 == 0 && mask2d_ld <= VQ_MAXLA, "x2_vqa_candidates: mask2d_ld=%d must be La=%d rounded up to 64",
+             mask2d_ld, La);
+  hipLaunchKernelGGL(vqa_candidates_kernel, dim3(B * K), dim3(VQ_THREADS), 0, (hipStream_t)stream, answer_ids, answer_atts, ids, Na, La, mask2d_ld,
+                     K, pad_token_id, input_ids, labels, kv_idx, mask2d);
+  return x2_check_launch("x2_vqa_candidates");
+}
+
+// ---------------------------------------------------------------------------------------------------------------- second stage
+// One workgroup per question, thread j = slot j.  The T = La - 1 losses of a row are added in index order in fp32, then subtracted from
+// the first-token log-probability.  The sort is by score (the probabilities are a monotone map of the scores, so they come out
+// non-increasing), lowest slot first among equal scores: slot j's rank is the number of slots that come before it.
+__global__ __launch_bounds__(VQ_THREADS) void vqa_rerank_kernel(const float* __restrict__ loss, int T, const float* __restrict__ vals,
+                                                                const int* __restrict__ ids, int K, float* __restrict__ topk_probs,
+                                                                int* __restrict__ topk_ids, float* __restrict__ scores) {
+  __shared__ float sScore[VQ_MAXK];
+  __shared__ float sRed[VQ_THREADS / 64];
+  const int b = blockIdx.x, j = threadIdx.x;
+  const bool live = j < K;
+  float sc = -INFINITY;
+  if (live) {
+    const float* lr = loss + ((size_t)b * K + j) * T;
+    float acc = 0.f;
+    for (int t = 0; t < T; ++t) acc += lr[t];
+    sc = vals[(size_t)b * K + j] - acc;
+    scores[(size_t)b * K + j] = sc;
+    sScore[j] = sc;
+  }
+  const float mx = vq_block_max(sc, sRed);                                 // the barrier inside also publishes sScore
+  const float e = live ? expf(sc - mx) : 0.f;
+  const float den = vq_block_sum(e, sRed);
+  if (live) {
+    int rank = 0;
+    for (int i = 0; i < K; ++i) rank += vq_better(sScore[i], i, sc, j) ? 1 : 0;
+    topk_probs[(size_t)b * K + rank] = e / den;
+    topk_ids[(size_t)b * K + rank] = ids[(size_t)b * K + j];
+  }
+}
+
+extern "C" int x2_vqa_rerank(const float* loss_rows, int T, const float* vals, const int* ids, int B, int K, float* topk_probs, int* topk_ids,
+                             float* scores, void* stream) {
+  X2_REQUIRE(loss_rows && vals && ids && topk_probs && topk_ids && scores, "x2_vqa_rerank: null tensor");
+  X2_REQUIRE(B >= 1 && K >= 1 && K <= VQ_MAXK, "x2_vqa_rerank: B=%d k=%d (k at most %d)", B, K, VQ_MAXK);
+  X2_REQUIRE(T >= 1 && T <= VQ_MAXLA - 1, "x2_vqa_rerank: La - 1 = %d must be in 1..%d", T, VQ_MAXLA - 1);
+  hipLaunchKernelGGL(vqa_rerank_kernel, dim3(B), dim3(VQ_THREADS), 0, (hipStream_t)stream, loss_rows, T, vals, ids, K, topk_probs, topk_ids, scores);
+  return x2_check_launch("x2_vqa_rerank");
+}

@@ -891,3 +891,67 @@ def logprob_topk(logits, V, k, *, seq=None, seq_len=0, ngram=0, eos_id=0, forbid
     call("x2_logprob_topk", ptr(logits), _rows(logits), V, S, ptr(seq), Lseq, seq_len, ngram, eos_id, 1 if forbid_eos else 0, k, ptr(vals),
          ptr(ids), ptr(logs))
     return vals, ids, logs
+
+
+# ----------------------------------------------------------------------------- VQA inference (csrc/vqa.hip)
+
+def mlm_ce_rows(x, E, bias, labels, V):
+    """The per-row half of mlm_ce_fwd: -> (loss_row fp32 [R] = lse - z[label], 0 where the label is negative; lse fp32 [R]) of z = x @ E^T + bias
+    over the first V columns, the logits never stored."""
+    assert x.dtype == BF16 and E.dtype == BF16 and x.shape[1] == E.shape[1] and bias.dtype == F32 and bias.numel() == E.shape[0]
+    assert labels.dtype == torch.int64 and labels.numel() == x.shape[0]
+    R, Hd = x.shape
+    Vp = E.shape[0]
+    dev = x.device
+    part = torch.empty(R, Vp // 64, 2, device=dev, dtype=F32)
+    small = torch.empty(3 * R + 2, device=dev, dtype=F32)
+    zlab, lse, rows, stat = small[:R], small[R:2 * R], small[2 * R:3 * R], small[3 * R:]
+    with _timed(2.0 * R * Vp * Hd):
+        call("x2_mlm_ce_fwd", ptr(x), ptr(E), ptr(bias), ptr(labels), R, Vp, V, Hd, _rows(x), _rows(E), ptr(part), ptr(zlab))
+    call("x2_ce_combine", ptr(part), Vp // 64, ptr(zlab), ptr(labels), R, ptr(lse), ptr(rows), ptr(stat))
+    return rows, lse
+
+
+def answer_topk(logits, V, first_tok, k):
+    """First ranking stage: per row of fp32 logits [B, ldv] (V valid columns) the k candidates with the largest log-probability of their first
+    token (first_tok int32 [Na], values in [0, V)): -> (vals fp32 [B, k] log-probabilities, ids int32 [B, k] candidate indices), largest
+    first, lowest candidate index first among equals.  1 <= k <= min(Na, 256), Na <= 65536."""
+    assert logits.dtype == F32 and logits.dim() == 2 and logits.stride(1) == 1
+    assert first_tok.dtype == torch.int32 and first_tok.dim() == 1 and first_tok.is_contiguous()
+    B, Na = logits.shape[0], first_tok.numel()
+    kk = max(int(k), 1)
+    vals = torch.empty(B, kk, device=logits.device, dtype=F32)
+    ids = torch.empty(B, kk, device=logits.device, dtype=torch.int32)
+    call("x2_answer_topk", ptr(logits), _rows(logits), V, B, ptr(first_tok), Na, int(k), ptr(vals), ptr(ids))
+    return vals, ids
+
+
+def vqa_candidates(answer_ids, answer_atts, ids, pad_token_id):
+    """The candidate rows of the second decoder pass in one launch: answer_ids / answer_atts int64 [Na, La], ids int32 [B, k] -> (input_ids int64
+    [S, La], labels int64 [S, La - 1] (next token, -100 at padding), kv_idx int32 [S] = s // k, mask2d fp32 [S, La, round_up(La, 64)] the
+    additive tril x padding mask of attn_fwd_mask2d), S = B * k."""
+    assert answer_ids.dtype == torch.int64 and answer_ids.dim() == 2 and answer_ids.is_contiguous()
+    assert answer_atts.dtype == torch.int64 and answer_atts.shape == answer_ids.shape and answer_atts.is_contiguous()
+    assert ids.dtype == torch.int32 and ids.dim() == 2 and ids.is_contiguous()
+    Na, La = answer_ids.shape
+    B, k = ids.shape
+    S, dev = B * k, ids.device
+    input_ids = torch.empty(S, La, device=dev, dtype=torch.int64)
+    labels = torch.empty(S, max(La - 1, 0), device=dev, dtype=torch.int64)
+    kv_idx = torch.empty(S, device=dev, dtype=torch.int32)
+    mask2d = torch.empty(S, La, round_up(La, 64), device=dev, dtype=F32)
+    call("x2_vqa_candidates", ptr(answer_ids), ptr(answer_atts), ptr(ids), Na, La, B, k, int(pad_token_id), ptr(input_ids), ptr(labels),
+         ptr(kv_idx), ptr(mask2d), mask2d.shape[2])
+    return input_ids, labels, kv_idx, mask2d
+
+
+def vqa_rerank(loss_rows, vals, ids):
+    """Second ranking stage: loss_rows fp32 [S, La - 1] (ce loss per scored position, 0 where ignored), vals fp32 / ids int32 [B, k] of
+    answer_topk -> (topk_probs fp32 [B, k], topk_ids int32 [B, k], scores fp32 [B, k]): scores = vals - row sums, softmax per question,
+    sorted by score, lowest slot first among equals; scores stay in slot order."""
+    assert vals.dtype == F32 and ids.dtype == torch.int32 and vals.shape == ids.shape and vals.dim() == 2 and vals.is_contiguous() and ids.is_contiguous()
+    B, k = vals.shape
+    assert loss_rows.dtype == F32 and loss_rows.dim() == 2 and loss_rows.shape[0] == B * k and loss_rows.is_contiguous()
+    probs, out_ids, scores = torch.empty_like(vals), torch.empty_like(ids), torch.empty_like(vals)
+    call("x2_vqa_rerank", ptr(loss_rows), loss_rows.shape[1], ptr(vals), ptr(ids), B, k, ptr(probs), ptr(out_ids), ptr(scores))
+    return probs, out_ids, scores

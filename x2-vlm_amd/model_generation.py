@@ -1,18 +1,23 @@
-"""Captioning fine-tune and inference on the MI355X stages (models/model_generation.py:54-397, Captioning_MLM.py).
+"""Captioning fine-tune and inference, VQA answer ranking on the MI355X stages (models/model_generation.py:54-619, Captioning_MLM.py, VQA.py).
 
   XVLMForMLMCaptioning   training forward: the label-smoothed, weight-normalised MLM loss of the UniLM-style captioning collate
                          generate / beam_search: beam search over cached K/V (decode.py), HIP device only
+  XVLMForVQA             forward(train=False) / rank_answer: the k candidate answers with the likeliest first token, re-ranked by the
+                         answer decoder's sequence log-probability, HIP device only; the training step is not built yet
 
 The text encoder runs every layer with the collate's [B, L, L] attention mask (tril, or FG-free: [MASK] columns zeroed but for their
 own diagonal entry) through the 2-D masked attention kernels, embeds explicit (repeating) position ids, and forms the loss inside the
 decoder GEMM (kernels.mlm_ls_fwd / _bwd): the [B * max_masks, vocab] logits are never written.
 """
+import copy
 import os
 from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 
+from . import kernels as K
+from .xbert import BertLMHeadModel
 from .xvlm import XVLMBase
 
 
@@ -151,3 +156,200 @@ class XVLMForMLMCaptioning(XVLMBase):
                                       ngram_size=ngram_size, _forced=_forced, _return_traces=_return_traces, _use_cache=_use_cache)
         finally:
             self.train(was_training)
+
+
+class XVLMForVQA(XVLMBase):
+    """The reference's generative VQA model, ranking a closed answer list at inference (model_generation.py:409-619): `text_encoder` is the
+    bare 12 + n layer BertModel reading the image, `text_decoder` a BertLMHeadModel of num_dec_layers layers, every one with cross-attention
+    to the question states.
+
+    rank_answer on the HIP path, no host synchronisation between its stages:
+      1. the decoder on the [B, 1] start ids and the full head on those B rows -> first-step logits [B, Vp] (kept: B x V is small)
+      2. kernels.answer_topk: log-softmax, gathered at the Na answers' first tokens, the k best per question (LOG-probabilities: the
+         reference's softmax(...).log() underflows below 1e-38)
+      3. kernels.vqa_candidates: ids, next-token labels, the row -> question map and the additive tril x padding mask of the S = B * k rows
+      4. ONE decoder pass over the S rows; the B question states are shared through kv_idx (cross-attention K/V projected once per
+         question, not per candidate - the reference's tile() without the copy)
+      5. the head's transform and kernels.mlm_ce_rows on positions 0 .. La - 2 of every row: loss per scored token, logits never stored
+      6. kernels.vqa_rerank: score = first-token log-probability - summed losses, softmax over k, sorted.
+    Ties (candidates sharing a first token tie exactly in stage 2): the lower candidate index / slot comes first, where torch.topk leaves
+    the order open."""
+
+    def __init__(self, config):
+        if config["text_encoder"] == "data/roberta-base":
+            raise NotImplementedError("RoBERTa text encoders / decoders are outside the X2VLM-base/large hot path")
+        super().__init__(config, load_vision_params=False, load_text_params=False, use_contrastive_loss=False, use_matching_loss=False,
+                         use_mlm_loss=False, use_bbox_loss=False, config_text=None)
+        assert isinstance(config["pad_token_id"], int)
+        self.pad_token_id = config["pad_token_id"]
+        config_enc = self.text_encoder.config
+        self.num_text_layers = config_enc.fusion_layer
+        self.num_cross_layers = config_enc.num_hidden_layers - config_enc.fusion_layer
+        assert config["num_dec_layers"] in [self.num_cross_layers, self.num_cross_layers // 2], "initialization not implemented"
+        self.num_dec_layers = config["num_dec_layers"]
+        config_dec = copy.deepcopy(config_enc)
+        config_dec.encoder_width = config_enc.hidden_size
+        config_dec.fusion_layer = 0
+        config_dec.num_hidden_layers = config["num_dec_layers"]
+        self.cross_encoder_width = config_enc.encoder_width          # the vision width
+        self.dec_encoder_width = config_enc.hidden_size
+        self.text_decoder = BertLMHeadModel(config=config_dec)
+        if config.get("large_lr_for_dec", False):
+            self.init_params = ["text_decoder." + n for n, _ in self.text_decoder.named_parameters()]
+        elif self.dec_encoder_width != self.cross_encoder_width:
+            self.init_params = ["text_decoder." + n for n, _ in self.text_decoder.named_parameters()
+                                if ("crossattention.self.key" in n) or ("crossattention.self.value" in n)]
+        else:
+            self.init_params = []
+
+    def map_pretrained_state(self, state_dict, text_encoder_name=""):
+        """A pre-training checkpoint's keys for this model, in place (model_generation.py:461-507): every key with a `bert.` infix also
+        appears without it (the bare text encoder's names); text_encoder.bert.* moves to text_decoder.bert.* - embeddings and head as
+        they are, layers >= num_text_layers renumbered from 0 (only the odd-numbered ones, in pairs, when the decoder has half the cross
+        layers), layers below dropped, cross-attention key / value dropped when the question width differs from the vision width."""
+        infix = "roberta." if "roberta" in text_encoder_name else "bert."
+        halved = self.num_dec_layers == self.num_cross_layers // 2
+        for key in list(state_dict.keys()):
+            if infix in key:
+                state_dict[key.replace(infix, "")] = state_dict[key]
+            if "text_encoder." not in key:
+                continue
+            target = key
+            if "layer." in key:
+                parts = key.split(".")
+                layer = int(parts[4])                                       # text_encoder.bert.encoder.layer.<n>
+                cross_kv = ("crossattention.self.key" in key) or ("crossattention.self.value" in key)
+                if layer < self.num_text_layers or (halved and layer % 2 == 0) or \
+                        (self.dec_encoder_width != self.cross_encoder_width and cross_kv):
+                    del state_dict[key]
+                    continue
+                if halved:
+                    parts[4] = str((layer - self.num_text_layers) // 2)
+                elif self.num_dec_layers == self.num_cross_layers:
+                    parts[4] = str(layer - self.num_text_layers)
+                else:
+                    raise ValueError
+                target = ".".join(parts)
+            state_dict[target.replace("text_encoder", "text_decoder")] = state_dict.pop(key)
+        return state_dict
+
+    def load_pretrained(self, ckpt_rpath, config, is_eval=False):
+        from . import checkpoint
+        if is_eval:
+            state_dict = checkpoint.load_pretrained(self, ckpt_rpath, config, is_eval=True)
+        else:
+            state_dict = checkpoint.load_pretrained(self, ckpt_rpath, config, load_text=False)
+            print("### Loading pretrained text encoder", flush=True)
+            self.map_pretrained_state(state_dict, config["text_encoder"])
+        msg = self.load_state_dict(state_dict, strict=False)
+        print("load checkpoint from %s" % ckpt_rpath)
+        print("missing_keys: ", [p for p in msg.missing_keys if "vision_encoder" not in p])
+        print("unexpected_keys: ", msg.unexpected_keys)
+        return msg
+
+    _HOST_PATH = "%s runs on the HIP path; a host (CPU) path is a possible follow-up and is not implemented"
+
+    def forward(self, image, quesiton, answer=None, k=None, weights=None, train=True, _fused=True, _stage1_ids=None, _return_traces=False):
+        """train=False: (topk_ids int64 [B, k] indices into the answer list, topk_probs fp32 [B, k]) for `image` [B, 3, R, R], the tokenised
+        questions (`quesiton`, the reference's spelling: .input_ids / .attention_mask [B, Lq]) and the tokenised answer LIST `answer`
+        ([Na, La], every row starting with the same start token).  Runs in eval mode under no_grad; the training flag is restored.  The
+        underscored keywords are rank_answer's test seam."""
+        if train:
+            raise NotImplementedError("XVLMForVQA.forward(train=True): the VQA training step (weighted per-sequence LM loss and its backward) "
+                                      "is the follow-up to answer ranking and is not implemented")
+        if not isinstance(image, torch.Tensor) or not image.is_cuda:
+            raise NotImplementedError(self._HOST_PATH % "XVLMForVQA.forward")
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                image_embeds, image_atts = self.get_vision_embeds(image)
+                question_states = self.text_encoder(quesiton.input_ids, attention_mask=quesiton.attention_mask,
+                                                    encoder_hidden_states=image_embeds, encoder_attention_mask=image_atts,
+                                                    return_dict=True).last_hidden_state
+                return self.rank_answer(question_states, quesiton.attention_mask, answer.input_ids, answer.attention_mask, k, _fused=_fused,
+                                        _stage1_ids=_stage1_ids, _return_traces=_return_traces)
+        finally:
+            self.train(was_training)
+
+    def rank_answer(self, question_states, question_atts, answer_ids, answer_atts, k, _fused=True, _stage1_ids=None, _return_traces=False):
+        """question_states [B, Lq, Hd] fp32, question_atts [B, Lq], answer_ids / answer_atts int64 [Na, La] -> (topk_ids int64 [B, k],
+        topk_probs fp32 [B, k]), best first.  1 <= k <= min(Na, 256), Na <= 65536, 2 <= La <= 128.
+
+        Test seam (not part of the mirrored API): _fused=False runs the same stages with the [S * (La - 1), V] logits materialised and the
+        candidate bookkeeping in torch (the measured baseline of probes/bench_vqa_rank.py); _stage1_ids int [B, k] replaces the first stage's
+        selection (their log-probabilities are looked up); _return_traces adds a dict: logits0 [B, V], logp_first [B, Na], stage1_logp /
+        stage1_ids [B, k], loss_rows [S, La - 1], scores [B, k] in stage-1 slot order."""
+        if not isinstance(question_states, torch.Tensor) or not question_states.is_cuda:
+            raise NotImplementedError(self._HOST_PATH % "XVLMForVQA.rank_answer")
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                return self._rank_answer(question_states, question_atts, answer_ids, answer_atts, int(k), _fused, _stage1_ids, _return_traces)
+        finally:
+            self.train(was_training)
+
+    def _rank_answer(self, question_states, question_atts, answer_ids, answer_atts, k, fused, stage1_ids, want_traces):
+        dec = self.text_decoder
+        V = dec.config.vocab_size
+        dev = question_states.device
+        B, Hd = question_states.shape[0], question_states.shape[2]
+        Na, La = answer_ids.shape
+        if not (1 <= k <= min(Na, 256) and Na <= 65536 and 2 <= La <= 128):
+            raise ValueError("rank_answer: k=%d Na=%d La=%d outside 1 <= k <= min(Na, 256), Na <= 65536, 2 <= La <= 128" % (k, Na, La))
+        answer_ids = answer_ids.to(torch.int64).contiguous()
+        answer_atts = answer_atts.to(torch.int64).contiguous()
+        question_states = question_states.contiguous()
+        start_ids = answer_ids[0, 0].repeat(B, 1)
+        h0 = dec(start_ids, encoder_hidden_states=question_states, encoder_attention_mask=question_atts).last_hidden_state
+        logits0 = dec.head_logits(K.cast_bf16(h0.reshape(B, Hd)))                                  # [B, Vp]
+        first_tok = answer_ids[:, 1].to(torch.int32).contiguous()
+        S = B * k
+        if fused:
+            vals, ids = K.answer_topk(logits0, V, first_tok, k)
+        if not fused or stage1_ids is not None or want_traces:
+            logp_first = torch.log_softmax(logits0[:, :V], -1).index_select(1, first_tok.long())
+        if not fused:
+            order = torch.sort(logp_first, dim=1, descending=True, stable=True).indices[:, :k]     # lowest candidate first among equals
+            vals, ids = torch.gather(logp_first, 1, order).contiguous(), order.to(torch.int32).contiguous()
+        if stage1_ids is not None:
+            ids = torch.as_tensor(stage1_ids, device=dev).reshape(B, k).to(torch.int32).contiguous()
+            vals = torch.gather(logp_first, 1, ids.long()).contiguous()
+        if fused:
+            input_ids, labels, kv_idx, mask2d = K.vqa_candidates(answer_ids, answer_atts, ids, self.pad_token_id)
+            atts = None
+        else:
+            flat = ids.reshape(S).long()
+            input_ids = answer_ids.index_select(0, flat)
+            atts = answer_atts.index_select(0, flat)
+            labels = input_ids[:, 1:].masked_fill(input_ids[:, 1:] == self.pad_token_id, -100).contiguous()
+            kv_idx = (torch.arange(S, device=dev, dtype=torch.int32) // k).contiguous()
+            mask2d = None
+        row_atts = question_atts.index_select(0, kv_idx.long())
+        h = dec(input_ids, attention_mask=atts, encoder_hidden_states=question_states, encoder_attention_mask=row_atts, kv_idx=kv_idx,
+                self_mask2d=mask2d).last_hidden_state                                               # [S, La, Hd]
+        cache = self.__dict__.setdefault("_scored_rows", {})
+        rows = cache.get((S, La, dev))
+        if rows is None:
+            rows = (torch.arange(S, device=dev, dtype=torch.int32).unsqueeze(1) * La
+                    + torch.arange(La - 1, device=dev, dtype=torch.int32)).reshape(-1).contiguous()
+            cache[(S, La, dev)] = rows
+        _, hb = K.gather_rows(h.reshape(S * La, Hd), rows, Hd, want_f32=False, want_bf16=True)
+        flat_labels = labels.reshape(-1)
+        if fused:
+            loss_rows, _ = dec.head_loss_rows(hb, flat_labels)
+            loss_rows = loss_rows.reshape(S, La - 1).contiguous()
+            topk_probs, topk_ids, scores = K.vqa_rerank(loss_rows, vals, ids)
+        else:
+            z = dec.head_logits(hb)[:, :V]
+            picked = torch.gather(z, 1, flat_labels.clamp(min=0).unsqueeze(1)).squeeze(1)
+            loss_rows = torch.where(flat_labels >= 0, torch.logsumexp(z, -1) - picked, torch.zeros_like(picked)).reshape(S, La - 1)
+            scores = vals - loss_rows.sum(1).reshape(B, k)
+            order = torch.sort(scores, dim=1, descending=True, stable=True).indices
+            topk_probs = torch.gather(torch.softmax(scores, -1), 1, order)
+            topk_ids = torch.gather(ids, 1, order)
+        out = (topk_ids.long(), topk_probs)
+        if want_traces:
+            out += (dict(logits0=logits0[:, :V], logp_first=logp_first, stage1_logp=vals, stage1_ids=ids, loss_rows=loss_rows, scores=scores),)
+        return out

@@ -227,3 +227,49 @@ def synth_captioning_batch(seed, batch, max_tokens, max_masks, image_res, vocab_
         mw[b, :k] = 1
     out = dict(image=image, text_ids_masked=ids_out, text_atts=atts, position_ids=pids, masked_pos=mpos, masked_ids=mids, masked_weight=mw)
     return {k_: torch.from_numpy(v) for k_, v in out.items()}
+
+
+def _vqa_first_tokens(r, vocab_size, n_answers):
+    """first token of every answer row: about n_answers / 3 distinct ids, every one used (the first draws of the answer list's stream)"""
+    lo = 1000 if vocab_size > 2000 else 5
+    n_first = max(1, int(round(n_answers / 3.0)))
+    firsts = lo + r.permutation(vocab_size - lo)[:n_first]
+    pick = np.concatenate([np.arange(n_first), r.integers(0, n_first, size=max(0, n_answers - n_first))])[:n_answers]
+    return firsts[pick[r.permutation(n_answers)]], n_first
+
+
+def synth_vqa_first_tokens(answer_seed, vocab_size, n_answers):
+    """The first tokens synth_vqa_batch(..., answer_seed=answer_seed) gives its answer rows, without building the rows (seed searches)."""
+    return _vqa_first_tokens(_rng(answer_seed, "vqa_answers"), vocab_size, n_answers)[0]
+
+
+def synth_vqa_batch(seed, batch, seq_len, image_res, vocab_size, n_answers, answer_len, answer_seed=None):
+    """VQA inference batch: `batch` images and ragged questions (synth_batch's image / text_ids / text_atts under `seed`) and the closed
+    answer list both ranking stages read, under `answer_seed` (None: `seed`): n_answers DISTINCT rows [CLS] t1 .. tn [SEP] padded with 0 to
+    answer_len, lengths 3 .. answer_len, the first tokens t1 drawn from about n_answers / 3 distinct ids (every one used), so candidates share
+    first tokens - and tie exactly in the first stage - the way a real answer list does.  Returns a dict of CPU tensors: image,
+    question_ids / question_atts (batch, seq_len), answer_ids / answer_atts (n_answers, answer_len), int64 but image."""
+    base = synth_batch(seed, batch, seq_len, image_res, vocab_size, max_masks=1, ragged=True)
+    r = _rng(seed if answer_seed is None else answer_seed, "vqa_answers")
+    big = vocab_size > 2000
+    cls_id, sep_id = (101, 102) if big else (1, 2)
+    lo = 1000 if big else 5
+    first_tok, n_first = _vqa_first_tokens(r, vocab_size, n_answers)
+    if answer_len < 4 and n_answers > n_first:
+        raise ValueError("synth_vqa_batch: answer_len %d leaves one row per first token, %d distinct rows are asked for" % (answer_len, n_answers))
+    ids = np.zeros((n_answers, answer_len), dtype=np.int64)
+    atts = np.zeros((n_answers, answer_len), dtype=np.int64)
+    seen = set()
+    for a in range(n_answers):
+        for _ in range(1000):
+            n = int(r.integers(3, answer_len + 1))
+            row = [cls_id, int(first_tok[a])] + [int(t) for t in r.integers(lo, vocab_size, size=n - 3)] + [sep_id]
+            if tuple(row) not in seen:
+                break
+        else:
+            raise ValueError("synth_vqa_batch: no distinct row found for answer %d" % a)
+        seen.add(tuple(row))
+        ids[a, :n] = row
+        atts[a, :n] = 1
+    return dict(image=base["image"], question_ids=base["text_ids"], question_atts=base["text_atts"], answer_ids=torch.from_numpy(ids),
+                answer_atts=torch.from_numpy(atts))

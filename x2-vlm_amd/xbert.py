@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from . import kernels as K
 from . import ops
-from .engine import BertLayersFn, EmbeddingsFn, MlmLossFn, _mask_pad, bert_layer_param_names
+from .engine import BANK, BertLayersFn, EmbeddingsFn, MlmLossFn, _mask_pad, bert_layer_param_names
 
 
 _FIXED_SEEDS = []
@@ -137,9 +137,10 @@ class BertEncoder(nn.Module):
         self.config = config
         self.layer = nn.ModuleList([BertLayer(config, i) for i in range(config.num_hidden_layers)])
 
-    def run(self, hidden, text_atts, enc=None, enc_atts=None, mode="multi_modal", kv_idx=None):
+    def run(self, hidden, text_atts, enc=None, enc_atts=None, mode="multi_modal", kv_idx=None, self_mask2d=None):
         """hidden (S,L,Hd) fp32; enc (Bi,T,Dv) image tokens shared through kv_idx (int (S,), None = identity);
-        enc_atts (S,T) per text row; text_atts (S,L) per key or (S,L,L) per (query, key)."""
+        enc_atts (S,T) per text row; text_atts (S,L) per key or (S,L,L) per (query, key); self_mask2d: the additive fp32
+        [S, L, round_up(L, 64)] mask already in attn_fwd_mask2d's layout (kernels.vqa_candidates), taking text_atts' place."""
         cfg = self.config
         lo, hi = {"text": (0, cfg.fusion_layer), "fusion": (cfg.fusion_layer, cfg.num_hidden_layers),
                   "multi_modal": (0, cfg.num_hidden_layers)}[mode]
@@ -150,7 +151,11 @@ class BertEncoder(nn.Module):
         meta = dict(lo=lo, hi=hi, fusion_at=cfg.fusion_layer, heads=cfg.num_attention_heads, eps=cfg.layer_norm_eps,
                     self_mask=None, self_mask2d=None, enc_mask=None, kv_idx=None,
                     seq_off=None, seq_ids=None, drop=drop)
-        meta["self_mask"], meta["self_mask2d"] = _text_masks(text_atts)
+        if self_mask2d is not None:
+            assert self_mask2d.dtype == torch.float32 and self_mask2d.shape == (S, L, K.round_up(L, 64)) and self_mask2d.is_contiguous()
+            meta["self_mask2d"] = self_mask2d
+        else:
+            meta["self_mask"], meta["self_mask2d"] = _text_masks(text_atts)
         cross = enc is not None and hi > cfg.fusion_layer
         if cross:
             Bi = enc.shape[0]
@@ -201,16 +206,18 @@ class BertModel(nn.Module):
         return self.embeddings.word_embeddings
 
     def forward(self, input_ids=None, attention_mask=None, encoder_embeds=None, encoder_hidden_states=None,
-                encoder_attention_mask=None, return_dict=True, mode="multi_modal", kv_idx=None, position_ids=None, **unused):
-        """xbert.py:1075-1220 (encoder path: no decoder cache, no head masks).  attention_mask (S,L) or (S,L,L)."""
+                encoder_attention_mask=None, return_dict=True, mode="multi_modal", kv_idx=None, position_ids=None, self_mask2d=None,
+                **unused):
+        """xbert.py:1075-1220 (encoder path: no decoder cache, no head masks).  attention_mask (S,L) or (S,L,L), or the prebuilt
+        additive self_mask2d of BertEncoder.run in its place."""
         _refuse_unused("BertModel", unused)
         hidden = self.embeddings(input_ids, position_ids) if encoder_embeds is None else encoder_embeds
         S, L = hidden.shape[:2]
-        if attention_mask is None:
+        if attention_mask is None and self_mask2d is None:
             attention_mask = torch.ones(S, L, device=hidden.device)
         if encoder_hidden_states is not None and encoder_attention_mask is None:
             encoder_attention_mask = torch.ones(S, encoder_hidden_states.shape[1], device=hidden.device)
-        out = self.encoder.run(hidden, attention_mask, encoder_hidden_states, encoder_attention_mask, mode, kv_idx)
+        out = self.encoder.run(hidden, attention_mask, encoder_hidden_states, encoder_attention_mask, mode, kv_idx, self_mask2d)
         return SimpleNamespace(last_hidden_state=out) if return_dict else (out,)
 
 
@@ -286,10 +293,70 @@ class BertForMaskedLM(nn.Module):
         return SimpleNamespace(loss=loss if labels is not None else None, logits=logits)
 
 
+class BertLMHeadModel(nn.Module):
+    """xbert.py:1268-1400, the causal answer decoder of XVLMForVQA: `bert` with cross-attention in every layer (config.fusion_layer = 0,
+    config.encoder_width = the question states' width) and the LM head `cls`, whose decoder.weight is tied to ITS OWN word embeddings.
+    Built for answer ranking (inference): forward returns the hidden states of a causal pass; head_logits / head_loss_rows apply the head
+    to gathered rows.  The LM loss of forward(labels=...) - the training step - is not implemented and refused."""
+
+    def __init__(self, config, label_smoothing=0.0):
+        super().__init__()
+        self.config = config
+        self.label_smoothing = label_smoothing
+        self.bert = BertModel(config)
+        self.cls = BertOnlyMLMHead(config)
+        self.apply(lambda m: _bert_init(m, config.initializer_range))
+        self.cls.predictions.decoder.weight = self.bert.embeddings.word_embeddings.weight
+        self.cls.predictions.decoder.bias = self.cls.predictions.bias      # one parameter under both names, as the reference serialises it
+
+    def get_output_embeddings(self):
+        return self.cls.predictions.decoder
+
+    def forward(self, input_ids=None, attention_mask=None, encoder_hidden_states=None, encoder_attention_mask=None, return_dict=True,
+                is_decoder=True, reduction="mean", mode="multi_modal", kv_idx=None, self_mask2d=None, **unused):
+        """-> last_hidden_state [S, L, Hd] of the causal pass.  The self-attention mask is tril x attention_mask [S, L] (None: ones), or
+        the additive self_mask2d kernels.vqa_candidates built from the same rule; encoder_hidden_states [Bq, T, Hd] may be shared by
+        several rows through kv_idx, encoder_attention_mask is per row [S, T]."""
+        _refuse_unused("BertLMHeadModel", unused)
+        if not is_decoder:
+            raise NotImplementedError("BertLMHeadModel.forward(is_decoder=False) is not supported by the HIP path")
+        S, L = input_ids.shape
+        if self_mask2d is None and L > 1:
+            atts = torch.ones(S, L, dtype=torch.long, device=input_ids.device) if attention_mask is None else attention_mask.long()
+            attention_mask = torch.tril(torch.ones(L, L, dtype=torch.long, device=input_ids.device)).unsqueeze(0) * atts.unsqueeze(1)
+        h = self.bert(input_ids, attention_mask=attention_mask, encoder_hidden_states=encoder_hidden_states,
+                      encoder_attention_mask=encoder_attention_mask, mode=mode, kv_idx=kv_idx, self_mask2d=self_mask2d).last_hidden_state
+        return SimpleNamespace(last_hidden_state=h) if return_dict else (h,)
+
+    def _head(self, rows):
+        """transform (dense + GELU + LayerNorm) of bf16 rows [R, Hd] -> (bf16 [R, Hd], padded bf16 embeddings [Vp, Hd], padded bias [Vp])"""
+        pr = self.cls.predictions
+        R, Hd = rows.shape
+        wd, _ = BANK.linear(pr.transform.dense.weight)
+        t_pre = torch.empty(R, Hd, device=rows.device, dtype=torch.bfloat16)
+        t_act = K.gemm_nt(rows, wd, bias=pr.transform.dense.bias, aux=t_pre, act=1, out_dtype=torch.float32)
+        tb = K.layernorm_fwd(t_act, pr.transform.LayerNorm.weight, pr.transform.LayerNorm.bias, self.config.layer_norm_eps)[0]
+        word = self.bert.embeddings.word_embeddings.weight
+        Eb, _ = BANK.vocab(word)
+        V, Vp = word.shape[0], Eb.shape[0]
+        return tb, Eb, (BANK.vector(pr.bias, Vp - V) if Vp > V else pr.bias.detach())
+
+    def head_logits(self, rows):
+        """fp32 logits [R, Vp] of bf16 hidden rows [R, Hd] (Vp = the vocabulary rounded up to 64; the padding columns mean nothing)"""
+        tb, Eb, bias = self._head(rows)
+        return K.gemm_nt(tb, Eb, bias=bias, out_dtype=torch.float32)
+
+    def head_loss_rows(self, rows, labels):
+        """(loss_row [R] = logsumexp - logit of the label, 0 where the label is negative; lse [R]) of bf16 hidden rows [R, Hd], the
+        logits staying in the GEMM (kernels.mlm_ce_rows)"""
+        tb, Eb, bias = self._head(rows)
+        return K.mlm_ce_rows(tb, Eb, bias, labels, self.config.vocab_size)
+
+
 def _refuse_unused(who, unused):
     """keyword arguments of the reference's signature this path does not implement raise instead of vanishing"""
     for k, v in unused.items():
-        if v not in (None, False):
+        if isinstance(v, torch.Tensor) or v not in (None, False):
             raise NotImplementedError("%s.forward(%s=...) is not supported by the HIP path" % (who, k))
 
 
