@@ -5,8 +5,9 @@ Here a step feeds [chosen token, [MASK]] (the first step: prompt + [MASK]) throu
   * a per-row, per-layer K/V cache indexed by ABSOLUTE position (kernels.attn_decode: the [MASK] of step t writes slot next_pos, the token
     chosen at t has that same position and overwrites it at t + 1 - the reference's dropping of the [MASK] state, without a copy),
   * the cross-attention K/V of the image tokens projected once per image per layer and shared by the beams through kv_idx,
-  * the MLM head on the [MASK] rows only, scored by kernels.logprob_topk (log-softmax, n-gram and EOS penalties, top-K: one launch, no host
-    round trip), and the caches reordered by the back pointers in one launch for all layers (kernels.beam_gather, ping-pong buffers).
+  * the MLM head on the [MASK] rows only (the text encoder's head_logits, xbert.LMHeadRows), scored by kernels.logprob_topk (log-softmax,
+    n-gram and EOS penalties, top-K: one launch, no host round trip), and the caches reordered by the back pointers in one launch for
+    all layers (kernels.beam_gather, ping-pong buffers).
 The beam bookkeeping (merge_beams) is torch on the device, without a host sync inside the loop; one transfer after it feeds backtrace().
 merge_beams and backtrace are pure functions usable on CPU tensors / lists; log_scores_reference and banned_tokens restate the scoring rule
 on the host for the tests."""
@@ -213,28 +214,12 @@ class _TextStack:
         if rows is None:
             rows = self.mask_rows[(R, n_new)] = (torch.arange(R, device=dev, dtype=torch.int32) * n_new + (n_new - 1)).contiguous()
         _, rb = K.gather_rows(h, rows, Hd, want_f32=False, want_bf16=True)
-        return mlm_logits(te, rb)
+        return te.head_logits(rb)
 
     def reorder(self, parent, hist):
         """caches[l][s][:hist] <- caches[l][parent[s]][:hist] into the other buffer, which becomes the current one."""
         K.beam_gather(self.caches[self.cur], self.caches[1 - self.cur], parent, hist)
         self.cur = 1 - self.cur
-
-
-def mlm_logits(te, rb):
-    """The MLM head (transform dense + GELU + LayerNorm, tied decoder + bias) on bf16 rows [R, Hd] -> fp32 logits [R, Vp] (Vp = the
-    vocabulary rounded up to 64; the padding columns hold the zero-padded decoder's output)."""
-    pr = te.cls.predictions
-    R, Hd = rb.shape
-    wd, _ = BANK.linear(pr.transform.dense.weight)
-    t_pre = torch.empty(R, Hd, device=rb.device, dtype=BF16)
-    t_act = K.gemm_nt(rb, wd, bias=pr.transform.dense.bias, aux=t_pre, act=1, out_dtype=F32)
-    tb = K.layernorm_fwd(t_act, pr.transform.LayerNorm.weight, pr.transform.LayerNorm.bias, te.config.layer_norm_eps)[0]
-    word = te.bert.embeddings.word_embeddings.weight
-    Eb, _ = BANK.vocab(word)
-    V, Vp = word.shape[0], Eb.shape[0]
-    bias_p = BANK.vector(pr.bias, Vp - V) if Vp > V else pr.bias.detach()
-    return K.gemm_nt(tb, Eb, bias=bias_p, out_dtype=F32)
 
 
 def _uncached_logits(model, image_embeds, ids, pids, kv_idx):
@@ -246,7 +231,7 @@ def _uncached_logits(model, image_embeds, ids, pids, kv_idx):
     enc_atts = torch.ones(R, image_embeds.shape[1], dtype=torch.long, device=ids.device)
     h = te.bert(ids, attention_mask=atts, position_ids=pids, encoder_hidden_states=image_embeds, encoder_attention_mask=enc_atts,
                 kv_idx=kv_idx).last_hidden_state
-    return mlm_logits(te, K.cast_bf16(h[:, -1, :].contiguous()))
+    return te.head_logits(K.cast_bf16(h[:, -1, :].contiguous()))
 
 
 @torch.no_grad()

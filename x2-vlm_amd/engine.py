@@ -1038,6 +1038,21 @@ class EmbeddingsFn(torch.autograd.Function):
 
 # ----------------------------------------------------------------------------- MLM head + loss
 
+def lm_head_transform(rb, eps, dw_, db_, lnw, lnb, dec_bias, word):
+    """The launches MlmLossFn.forward starts with, for the inference heads (xbert.LMHeadRows) on bf16 rows rb [R, Hd]: dense + GELU, LayerNorm,
+    the zero-padded bf16 embeddings of the tied decoder and its bias padded to Vp = V rounded up to 64.
+    -> (tb bf16 [R, Hd], t_pre, t_act, mean, rstd, Eb [Vp, Hd], EbT [Hd, Vp], bias_p fp32 [Vp])."""
+    R, Hd = rb.shape
+    wd, _ = BANK.linear(dw_)
+    t_pre = torch.empty(R, Hd, device=rb.device, dtype=BF16)
+    t_act = K.gemm_nt(rb, wd, bias=db_, aux=t_pre, act=1, out_dtype=F32)
+    tb, _, mean, rstd = K.layernorm_fwd(t_act, lnw, lnb, eps)
+    Eb, EbT = BANK.vocab(word)
+    V, Vp = word.shape[0], Eb.shape[0]
+    bias_p = BANK.vector(dec_bias, Vp - V) if Vp > V else dec_bias.detach()
+    return tb, t_pre, t_act, mean, rstd, Eb, EbT, bias_p
+
+
 class MlmLossFn(torch.autograd.Function):
     """rows (R,Hd) fp32 at the masked positions -> mean CE over labels != -100.
     transform dense + GELU + LayerNorm, decoder tied to the word embeddings + bias

@@ -9,6 +9,7 @@ The text encoder runs every layer with the collate's [B, L, L] attention mask (t
 own diagonal entry) through the 2-D masked attention kernels, embeds explicit (repeating) position ids, and forms the loss inside the
 decoder GEMM (kernels.mlm_ls_fwd / _bwd): the [B * max_masks, vocab] logits are never written.
 """
+import contextlib
 import copy
 import os
 from types import SimpleNamespace
@@ -19,6 +20,38 @@ import torch.nn as nn
 from . import kernels as K
 from .xbert import BertLMHeadModel
 from .xvlm import XVLMBase
+
+
+_HOST_PATH = "%s runs on the HIP path; a host (CPU) path is a possible follow-up and is not implemented"
+
+
+@contextlib.contextmanager
+def _inference(model):
+    """eval mode under no_grad; the training flag is restored"""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            yield
+    finally:
+        model.train(was_training)
+
+
+def _load_pretrained(model, ckpt_rpath, config, is_eval, remap=None, hide=None):
+    """load_pretrained of both models: the checkpoint through checkpoint.load_pretrained (a pre-training one, is_eval False, without its
+    text parameters' renaming and then through `remap`), loaded non-strictly; missing keys containing `hide` are not printed."""
+    from . import checkpoint
+    if is_eval:
+        state_dict = checkpoint.load_pretrained(model, ckpt_rpath, config, is_eval=True)
+    else:
+        state_dict = checkpoint.load_pretrained(model, ckpt_rpath, config, load_text=False)
+        if remap is not None:
+            remap(state_dict)
+    msg = model.load_state_dict(state_dict, strict=False)
+    print("load checkpoint from %s" % ckpt_rpath)
+    print("missing_keys: ", [p for p in msg.missing_keys if hide is None or hide not in p])
+    print("unexpected_keys: ", msg.unexpected_keys)
+    return msg
 
 
 class _SmoothedTarget(nn.Module):
@@ -75,15 +108,7 @@ class XVLMForMLMCaptioning(XVLMBase):
         self.crit_mask_lm_smoothed = _SmoothedTarget(self.label_smoothing, self.tgt_vocab_size, self.ignore_index)
 
     def load_pretrained(self, ckpt_rpath, config, is_eval=False):
-        from . import checkpoint
-        if is_eval:
-            state_dict = checkpoint.load_pretrained(self, ckpt_rpath, config, is_eval=True)
-        else:
-            state_dict = checkpoint.load_pretrained(self, ckpt_rpath, config, load_text=False)
-        msg = self.load_state_dict(state_dict, strict=False)
-        print("load checkpoint from %s" % ckpt_rpath)
-        print("missing_keys: ", [p for p in msg.missing_keys])
-        print("unexpected_keys: ", msg.unexpected_keys)
+        _load_pretrained(self, ckpt_rpath, config, is_eval)
 
     def forward(self, image, input_ids_masked, attention_mask, position_ids, masked_pos, masked_ids, masked_weight):
         loss, _ = self.forward_with_scores(image, input_ids_masked, attention_mask, position_ids, masked_pos, masked_ids, masked_weight)
@@ -103,8 +128,6 @@ class XVLMForMLMCaptioning(XVLMBase):
             scores = logits[:, :self.tgt_vocab_size].reshape(masked_pos.shape[0], masked_pos.shape[1], -1)
         return loss, scores
 
-    _HOST_PATH = "%s runs on the HIP path; a host (CPU) path is a possible follow-up and is not implemented"
-
     def generate(self, image, num_beams=3, min_length=5, max_length=20, length_penalty=0, forbid_duplicate_ngrams=True, ngram_size=3):
         """Captions of `image` [B, 3, R, R] (a HIP tensor) by beam search: decoded strings with a real tokenizer, the id lists with the
         fallback tokenizer namespace (which needs config["eos_token_id"] and config["mask_token_id"]).
@@ -113,7 +136,7 @@ class XVLMForMLMCaptioning(XVLMBase):
         length - so the search runs bsz + max_length - len(prompt_ids) steps.  Kept as it is (the goldens come from the real reference);
         like the reference there is no early exit when every beam has ended."""
         if not isinstance(image, torch.Tensor) or not image.is_cuda:
-            raise NotImplementedError(self._HOST_PATH % "generate")
+            raise NotImplementedError(_HOST_PATH % "generate")
         from . import decode
         dev, batch = image.device, image.shape[0]
         prompt = torch.tensor([self.prompt_ids] * batch, dtype=torch.long, device=dev)
@@ -145,17 +168,13 @@ class XVLMForMLMCaptioning(XVLMBase):
         V <= 1024 and the [MASK]-row logits, plus the [T, B, K] total_scores / step_ids / back_ptrs; _use_cache=False recomputes the whole
         prefix every step through the full-sequence forward (the measured baseline)."""
         if not isinstance(image, torch.Tensor) or not image.is_cuda:
-            raise NotImplementedError(self._HOST_PATH % "beam_search")
+            raise NotImplementedError(_HOST_PATH % "beam_search")
         self.generation_token_ids()
         from . import decode
-        was_training = self.training
-        self.eval()
-        try:
+        with _inference(self):
             return decode.beam_search(self, image, input_ids, token_type_ids, position_ids, attention_mask, num_beams=num_beams,
                                       min_length=min_length, length_penalty=length_penalty, forbid_duplicate_ngrams=forbid_duplicate_ngrams,
                                       ngram_size=ngram_size, _forced=_forced, _return_traces=_return_traces, _use_cache=_use_cache)
-        finally:
-            self.train(was_training)
 
 
 class XVLMForVQA(XVLMBase):
@@ -234,20 +253,10 @@ class XVLMForVQA(XVLMBase):
         return state_dict
 
     def load_pretrained(self, ckpt_rpath, config, is_eval=False):
-        from . import checkpoint
-        if is_eval:
-            state_dict = checkpoint.load_pretrained(self, ckpt_rpath, config, is_eval=True)
-        else:
-            state_dict = checkpoint.load_pretrained(self, ckpt_rpath, config, load_text=False)
+        def remap(state_dict):
             print("### Loading pretrained text encoder", flush=True)
             self.map_pretrained_state(state_dict, config["text_encoder"])
-        msg = self.load_state_dict(state_dict, strict=False)
-        print("load checkpoint from %s" % ckpt_rpath)
-        print("missing_keys: ", [p for p in msg.missing_keys if "vision_encoder" not in p])
-        print("unexpected_keys: ", msg.unexpected_keys)
-        return msg
-
-    _HOST_PATH = "%s runs on the HIP path; a host (CPU) path is a possible follow-up and is not implemented"
+        return _load_pretrained(self, ckpt_rpath, config, is_eval, remap, hide="vision_encoder")
 
     def forward(self, image, quesiton, answer=None, k=None, weights=None, train=True, _fused=True, _stage1_ids=None, _return_traces=False):
         """train=False: (topk_ids int64 [B, k] indices into the answer list, topk_probs fp32 [B, k]) for `image` [B, 3, R, R], the tokenised
@@ -258,19 +267,13 @@ class XVLMForVQA(XVLMBase):
             raise NotImplementedError("XVLMForVQA.forward(train=True): the VQA training step (weighted per-sequence LM loss and its backward) "
                                       "is the follow-up to answer ranking and is not implemented")
         if not isinstance(image, torch.Tensor) or not image.is_cuda:
-            raise NotImplementedError(self._HOST_PATH % "XVLMForVQA.forward")
-        was_training = self.training
-        self.eval()
-        try:
-            with torch.no_grad():
-                image_embeds, image_atts = self.get_vision_embeds(image)
-                question_states = self.text_encoder(quesiton.input_ids, attention_mask=quesiton.attention_mask,
-                                                    encoder_hidden_states=image_embeds, encoder_attention_mask=image_atts,
-                                                    return_dict=True).last_hidden_state
-                return self.rank_answer(question_states, quesiton.attention_mask, answer.input_ids, answer.attention_mask, k, _fused=_fused,
-                                        _stage1_ids=_stage1_ids, _return_traces=_return_traces)
-        finally:
-            self.train(was_training)
+            raise NotImplementedError(_HOST_PATH % "XVLMForVQA.forward")
+        with _inference(self):
+            image_embeds, image_atts = self.get_vision_embeds(image)
+            question_states = self.text_encoder(quesiton.input_ids, attention_mask=quesiton.attention_mask, encoder_hidden_states=image_embeds,
+                                                encoder_attention_mask=image_atts, return_dict=True).last_hidden_state
+            return self.rank_answer(question_states, quesiton.attention_mask, answer.input_ids, answer.attention_mask, k, _fused=_fused,
+                                    _stage1_ids=_stage1_ids, _return_traces=_return_traces)
 
     def rank_answer(self, question_states, question_atts, answer_ids, answer_atts, k, _fused=True, _stage1_ids=None, _return_traces=False):
         """question_states [B, Lq, Hd] fp32, question_atts [B, Lq], answer_ids / answer_atts int64 [Na, La] -> (topk_ids int64 [B, k],
@@ -281,14 +284,9 @@ class XVLMForVQA(XVLMBase):
         selection (their log-probabilities are looked up); _return_traces adds a dict: logits0 [B, V], logp_first [B, Na], stage1_logp /
         stage1_ids [B, k], loss_rows [S, La - 1], scores [B, k] in stage-1 slot order."""
         if not isinstance(question_states, torch.Tensor) or not question_states.is_cuda:
-            raise NotImplementedError(self._HOST_PATH % "XVLMForVQA.rank_answer")
-        was_training = self.training
-        self.eval()
-        try:
-            with torch.no_grad():
-                return self._rank_answer(question_states, question_atts, answer_ids, answer_atts, int(k), _fused, _stage1_ids, _return_traces)
-        finally:
-            self.train(was_training)
+            raise NotImplementedError(_HOST_PATH % "XVLMForVQA.rank_answer")
+        with _inference(self):
+            return self._rank_answer(question_states, question_atts, answer_ids, answer_atts, int(k), _fused, _stage1_ids, _return_traces)
 
     def _rank_answer(self, question_states, question_atts, answer_ids, answer_atts, k, fused, stage1_ids, want_traces):
         dec = self.text_decoder

@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from . import kernels as K
 from . import ops
-from .engine import BANK, BertLayersFn, EmbeddingsFn, MlmLossFn, _mask_pad, bert_layer_param_names
+from .engine import BertLayersFn, EmbeddingsFn, MlmLossFn, _mask_pad, bert_layer_param_names, lm_head_transform
 
 
 _FIXED_SEEDS = []
@@ -242,7 +242,32 @@ class BertOnlyMLMHead(nn.Module):
         self.predictions = BertLMPredictionHead(config)
 
 
-class BertForMaskedLM(nn.Module):
+class LMHeadRows:
+    """The LM head `cls` (transform + decoder tied to the word embeddings of `bert`) applied to gathered bf16 rows at inference, for the two
+    models that carry one."""
+
+    def _head(self, rows):
+        """-> (transformed bf16 rows [R, Hd], padded bf16 embeddings [Vp, Hd], padded bias [Vp]) of bf16 hidden rows [R, Hd]"""
+        pr = self.cls.predictions
+        tb, _, _, _, _, Eb, _, bias_p = lm_head_transform(rows, self.config.layer_norm_eps, pr.transform.dense.weight, pr.transform.dense.bias,
+                                                          pr.transform.LayerNorm.weight, pr.transform.LayerNorm.bias, pr.bias,
+                                                          self.bert.embeddings.word_embeddings.weight)
+        return tb, Eb, bias_p
+
+    def head_logits(self, rows):
+        """fp32 logits [R, Vp] of bf16 hidden rows [R, Hd] (Vp = the vocabulary rounded up to 64; the padding columns hold the zero-padded
+        decoder's output and mean nothing)"""
+        tb, Eb, bias = self._head(rows)
+        return K.gemm_nt(tb, Eb, bias=bias, out_dtype=torch.float32)
+
+    def head_loss_rows(self, rows, labels):
+        """(loss_row [R] = logsumexp - logit of the label, 0 where the label is negative; lse [R]) of bf16 hidden rows [R, Hd], the
+        logits staying in the GEMM (kernels.mlm_ce_rows)"""
+        tb, Eb, bias = self._head(rows)
+        return K.mlm_ce_rows(tb, Eb, bias, labels, self.config.vocab_size)
+
+
+class BertForMaskedLM(nn.Module, LMHeadRows):
     """xbert.py:1567-1673.  decoder.weight is tied to the word embeddings (HF tie_weights)."""
 
     def __init__(self, config):
@@ -293,7 +318,7 @@ class BertForMaskedLM(nn.Module):
         return SimpleNamespace(loss=loss if labels is not None else None, logits=logits)
 
 
-class BertLMHeadModel(nn.Module):
+class BertLMHeadModel(nn.Module, LMHeadRows):
     """xbert.py:1268-1400, the causal answer decoder of XVLMForVQA: `bert` with cross-attention in every layer (config.fusion_layer = 0,
     config.encoder_width = the question states' width) and the LM head `cls`, whose decoder.weight is tied to ITS OWN word embeddings.
     Built for answer ranking (inference): forward returns the hidden states of a causal pass; head_logits / head_loss_rows apply the head
@@ -327,30 +352,6 @@ class BertLMHeadModel(nn.Module):
         h = self.bert(input_ids, attention_mask=attention_mask, encoder_hidden_states=encoder_hidden_states,
                       encoder_attention_mask=encoder_attention_mask, mode=mode, kv_idx=kv_idx, self_mask2d=self_mask2d).last_hidden_state
         return SimpleNamespace(last_hidden_state=h) if return_dict else (h,)
-
-    def _head(self, rows):
-        """transform (dense + GELU + LayerNorm) of bf16 rows [R, Hd] -> (bf16 [R, Hd], padded bf16 embeddings [Vp, Hd], padded bias [Vp])"""
-        pr = self.cls.predictions
-        R, Hd = rows.shape
-        wd, _ = BANK.linear(pr.transform.dense.weight)
-        t_pre = torch.empty(R, Hd, device=rows.device, dtype=torch.bfloat16)
-        t_act = K.gemm_nt(rows, wd, bias=pr.transform.dense.bias, aux=t_pre, act=1, out_dtype=torch.float32)
-        tb = K.layernorm_fwd(t_act, pr.transform.LayerNorm.weight, pr.transform.LayerNorm.bias, self.config.layer_norm_eps)[0]
-        word = self.bert.embeddings.word_embeddings.weight
-        Eb, _ = BANK.vocab(word)
-        V, Vp = word.shape[0], Eb.shape[0]
-        return tb, Eb, (BANK.vector(pr.bias, Vp - V) if Vp > V else pr.bias.detach())
-
-    def head_logits(self, rows):
-        """fp32 logits [R, Vp] of bf16 hidden rows [R, Hd] (Vp = the vocabulary rounded up to 64; the padding columns mean nothing)"""
-        tb, Eb, bias = self._head(rows)
-        return K.gemm_nt(tb, Eb, bias=bias, out_dtype=torch.float32)
-
-    def head_loss_rows(self, rows, labels):
-        """(loss_row [R] = logsumexp - logit of the label, 0 where the label is negative; lse [R]) of bf16 hidden rows [R, Hd], the
-        logits staying in the GEMM (kernels.mlm_ce_rows)"""
-        tb, Eb, bias = self._head(rows)
-        return K.mlm_ce_rows(tb, Eb, bias, labels, self.config.vocab_size)
 
 
 def _refuse_unused(who, unused):
