@@ -165,6 +165,8 @@ int x2_layerscale_finish(const int64_t* desc, int count, void* stream);
 int x2_rowscale_cast_colsum(const float* dx, const float* rowscale, void* dx_bf16, float* colsum, int M, int D,
                             float* ws /* [ceil(M/32)][D] */, int defer, void* stream);
 int x2_cast_bf16(const float* src, void* dst, long n, void* stream);
+/* src [R][C] fp32 -> dst [R][C] bf16 (or NULL) and dstT [C][ldt] bf16 = src^T, ldt >= R: columns R..ldt-1 of dstT are left untouched (a caller that
+ * reads them as padding zeroes them once) */
 int x2_cast_transpose_bf16(const float* src, void* dst, void* dstT, int R, int C, int ldt, void* stream);
 /* bf16 (W, W^T) copies of many fp32 weights in one launch (what apex O1's per-call weight casts amount to, done once per
  * optimizer step): desc = count rows of 8 int64 {src, dst, dstT, R, C, ldt, roff, tscale}: src [R][C] fp32 -> rows roff.. of
