@@ -20,7 +20,7 @@ conf = bench.CONFIGS[args.config]
 mp = importlib.import_module("x2-vlm_amd.model_pretrain")
 cfgs = importlib.import_module("x2-vlm_amd.configs")
 graph = importlib.import_module("x2-vlm_amd.graph")
-lib = importlib.import_module("x2-vlm_amd._lib").lib()
+tuned = importlib.import_module("x2-vlm_amd._lib").tuned
 dev = torch.device("cuda", 0)
 torch.manual_seed(0)
 cfg = cfgs.pretrain_config(tempfile.mkdtemp(), conf["size"], conf["res"])
@@ -43,25 +43,22 @@ for v in args.variants:
 res = {n: [] for n, _, _ in variants}
 for rnd in range(args.rounds):
     for name, knobs, env in variants:
-        for k, val in knobs.items():
-            assert lib.x2_tune(k, val) == 0, lib.x2_last_error()
-        old = {k: os.environ.get(k) for k in env}
-        os.environ.update(env)
-        step = graph.SegmentedStep(model, batch, warmup=1)
-        assert step.mode == "hipgraph-segments", step.error
-        for _ in range(args.warmup):
-            step()
-        torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(args.steps):
-            step()
-        b.record()
-        torch.cuda.synchronize()
-        res[name].append(a.elapsed_time(b) / args.steps)
-        del step
-        for k in knobs:
-            lib.x2_tune(k, 0)
+        with tuned(knobs):
+            old = {k: os.environ.get(k) for k in env}
+            os.environ.update(env)
+            step = graph.SegmentedStep(model, batch, warmup=1)
+            assert step.mode == "hipgraph-segments", step.error
+            for _ in range(args.warmup):
+                step()
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(args.steps):
+                step()
+            b.record()
+            torch.cuda.synchronize()
+            res[name].append(a.elapsed_time(b) / args.steps)
+            del step
         for k, v in old.items():
             if v is None:
                 os.environ.pop(k, None)

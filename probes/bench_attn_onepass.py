@@ -5,7 +5,7 @@ import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 K = importlib.import_module("x2-vlm_amd.kernels")
-lib = importlib.import_module("x2-vlm_amd._lib").lib()
+tuned = importlib.import_module("x2-vlm_amd._lib").tuned
 dev = "cuda"
 
 
@@ -53,9 +53,8 @@ for name, B, H, N in (("base step  B=64 H=12 N=197", 64, 12, 197), ("half batch 
     t = {0: [], 1: []}
     for _ in range(3):
         for knob in (1, 0):
-            lib.x2_tune(14, knob)
-            t[knob].append(timeit(bwd))
-    lib.x2_tune(14, 0)
+            with tuned({14: knob}):
+                t[knob].append(timeit(bwd))
     fl = 4.0 * B * H * N * N * 64 * 2.5
     print("%-28s two kernels %6.1f   one pass %6.1f   (%+.1f %%; %4.0f -> %4.0f TFLOP/s of the 5-product count)" % (
         name, min(t[1]), min(t[0]), 100 * (min(t[0]) / min(t[1]) - 1), fl / min(t[1]) / 1e6, fl / min(t[0]) / 1e6))
@@ -96,8 +95,7 @@ for name, drop in (("fusion cross, no dropout", None), ("fusion cross, dropout 0
     t = {0: [], 1: []}
     for _ in range(3):
         for knob in (1, 0):
-            lib.x2_tune(14, knob)
-            t[knob].append(timeit(bwd))
-    lib.x2_tune(14, 0)
+            with tuned({14: knob}):
+                t[knob].append(timeit(bwd))
     print("%-28s two kernels %6.1f   one pass %6.1f   (%+.1f %%; at most %d sequences on one image)" % (
         name, min(t[1]), min(t[0]), 100 * (min(t[0]) / min(t[1]) - 1), most))

@@ -7,6 +7,7 @@ import torch
 
 K = importlib.import_module("x2-vlm_amd.kernels")
 lib = importlib.import_module("x2-vlm_amd._lib").lib()
+tuned = importlib.import_module("x2-vlm_amd._lib").tuned
 dev = "cuda"
 
 
@@ -46,37 +47,32 @@ def nt_case(M, N, Kd, epi):
 def main():
     knobs = [int(x) for x in (sys.argv[1].split(",") if len(sys.argv) > 1 else ["1", "2", "3"])]
     print("NT GEMM, knob3 (1 = 128x128 tile, 2 = 192x128, 3 = 64x128; all 4 waves, 2-3 workgroups / CU) in", knobs)
-    lib.x2_tune(1, 1)
-    for name, M, N, Kd, epi in NT:
-        fn = nt_case(M, N, Kd, epi)
-        res = []
-        for g in knobs:
-            lib.x2_tune(3, g)
-            res.append(timeit(fn))
-        fl = 2.0 * M * N * Kd
-        print("  %-11s M=%5d N=%5d K=%4d %-5s " % (name, M, N, Kd, epi) + "  ".join("g%-2d %6.1fus %5.0fTF" % (g, t, fl / t / 1e6) for g, t in zip(knobs, res)))
-    lib.x2_tune(3, 0)
-    print("write-through (sc1) output stores: knob2 = 0 plain, 16 sc1 (interleaved rounds)")
-    for name, M, N, Kd, epi in NT:
-        fn = nt_case(M, N, Kd, epi)
-        res = {0: [], 16: []}
-        for rep in range(3):
-            for g in (0, 16):
-                lib.x2_tune(2, g)
-                res[g].append(timeit(fn, 10))
-        lib.x2_tune(2, 0)
-        print("  %-11s plain %6.1fus  sc1 %6.1fus" % (name, min(res[0]), min(res[16])))
-    lib.x2_tune(3, 1)
-    print("ablation on the 128x128 kernel (knob2: 0 full, 4 no epilogue)")
-    for name, M, N, Kd, epi in NT[:5]:
-        fn = nt_case(M, N, Kd, epi)
-        res = []
-        for g in (0, 4):
-            lib.x2_tune(2, g)
-            res.append((g, timeit(fn)))
-        lib.x2_tune(2, 0)
-        print("  %-11s " % name + "  ".join("d%d %6.1fus" % r for r in res))
-    lib.x2_tune(1, 0); lib.x2_tune(3, 0)
+    with tuned({1: 1}):
+        for name, M, N, Kd, epi in NT:
+            fn = nt_case(M, N, Kd, epi)
+            res = []
+            for g in knobs:
+                with tuned({3: g}):
+                    res.append(timeit(fn))
+            fl = 2.0 * M * N * Kd
+            print("  %-11s M=%5d N=%5d K=%4d %-5s " % (name, M, N, Kd, epi) + "  ".join("g%-2d %6.1fus %5.0fTF" % (g, t, fl / t / 1e6) for g, t in zip(knobs, res)))
+        print("write-through (sc1) output stores: knob2 = 0 plain, 16 sc1 (interleaved rounds)")
+        for name, M, N, Kd, epi in NT:
+            fn = nt_case(M, N, Kd, epi)
+            res = {0: [], 16: []}
+            for rep in range(3):
+                for g in (0, 16):
+                    with tuned({2: g}):
+                        res[g].append(timeit(fn, 10))
+            print("  %-11s plain %6.1fus  sc1 %6.1fus" % (name, min(res[0]), min(res[16])))
+        print("ablation on the 128x128 kernel (knob2: 0 full, 4 no epilogue)")
+        for name, M, N, Kd, epi in NT[:5]:
+            fn = nt_case(M, N, Kd, epi)
+            res = []
+            for g in (0, 4):
+                with tuned({3: 1, 2: g}):
+                    res.append((g, timeit(fn)))
+            print("  %-11s " % name + "  ".join("d%d %6.1fus" % r for r in res))
     print("TN grouped (weight grads)")
     for name, Mc, probs in [("vit block", 12608, [(768, 3072), (3072, 768), (768, 768), (2304, 768)]),
                             ("text layer", 3840, [(768, 3072), (3072, 768), (768, 768), (2304, 768)]),

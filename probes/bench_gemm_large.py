@@ -4,7 +4,7 @@ import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from _lib_helpers import timeit
-from bench_gemm import nt_case, lib  # noqa
+from bench_gemm import nt_case, tuned  # noqa
 SHAPES = [("L qkv", 18464, 3072, 1024, "bias"), ("L proj", 18464, 1024, 1024, "resid"), ("L fc1", 18464, 4096, 1024, "gelu"),
           ("L fc2", 18464, 1024, 4096, "resid"), ("L dqkv", 18464, 1024, 3072, "f32"), ("L datt", 18464, 1024, 1024, "bias"),
           ("L dpre", 18464, 4096, 1024, "gelu"), ("L t.qkv", 1920, 3072, 1024, "bias"), ("L t.ffn1", 1920, 4096, 1024, "gelu"),
@@ -15,8 +15,7 @@ for name, M, N, Kd, epi in SHAPES:
     best = {}
     for rep in range(2):
         for g in (0, 1, 2, 3):
-            lib.x2_tune(3, g)
-            best[g] = min(timeit(fn, 10), best.get(g, 1e9))
-    lib.x2_tune(3, 0)
+            with tuned({3: g}):
+                best[g] = min(timeit(fn, 10), best.get(g, 1e9))
     fl = 2.0 * M * N * Kd
     print("%-9s M=%5d N=%5d K=%4d  " % (name, M, N, Kd) + "  ".join("k%d %6.1fus %4.0fTF" % (g, best[g], fl / best[g] / 1e6) for g in sorted(best)), flush=True)

@@ -5,7 +5,7 @@ import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 K = importlib.import_module("x2-vlm_amd.kernels")
-lib = importlib.import_module("x2-vlm_amd._lib").lib()
+tuned = importlib.import_module("x2-vlm_amd._lib").tuned
 dev = "cuda"
 SHAPES = [("vision", 12608, 768, True, False), ("text 2B", 3840, 768, True, True), ("fusion 4B", 7680, 768, True, True),
           ("large vision", 18464, 1024, True, False), ("large fusion", 3840, 1024, True, True)]
@@ -34,15 +34,14 @@ for name, M, D, wb, wf in SHAPES:
     res = {}
     for rnd in range(3):
         for k in (1, 2, 4, 0):
-            lib.x2_tune(13, k)
-            t = timeit(lambda i: K.layernorm_fwd(xs[i], w, b, 1e-6, want_bf16=wb, want_f32=wf, y_bf16=yb[i], y_f32=yf[i]))
-            res[k] = min(res.get(k, 1e9), t)
-            out = K.layernorm_fwd(xs[0], w, b, 1e-6, want_bf16=True, want_f32=True)
-            torch.cuda.synchronize()
+            with tuned({13: k}):
+                t = timeit(lambda i: K.layernorm_fwd(xs[i], w, b, 1e-6, want_bf16=wb, want_f32=wf, y_bf16=yb[i], y_f32=yf[i]))
+                res[k] = min(res.get(k, 1e9), t)
+                out = K.layernorm_fwd(xs[0], w, b, 1e-6, want_bf16=True, want_f32=True)
+                torch.cuda.synchronize()
             if ref is None:
                 ref = [o.clone() for o in out]
             else:
                 assert all(torch.equal(o, r) for o, r in zip(out, ref)), (name, k)
-    lib.x2_tune(13, 0)
     mb = M * D * (4 + 2 + (4 if wf else 0)) / 1e6
     print("%-14s M=%6d D=%5d %6.1f MB | " % (name, M, D, mb) + "  ".join("rpw%d %6.1f us %5.2f TB/s" % (k, res[k], mb / res[k]) for k in (1, 2, 4, 0)))

@@ -11,7 +11,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 K = importlib.import_module("x2-vlm_amd.kernels")
-lib = importlib.import_module("x2-vlm_amd._lib").lib()
+tuned = importlib.import_module("x2-vlm_amd._lib").tuned
 dev = "cuda"
 
 
@@ -87,16 +87,14 @@ def main():
         res = {c[0]: [] for c in configs}
         for _ in range(3):
             for cname, k1, k3 in configs:
-                lib.x2_tune(1, k1); lib.x2_tune(3, k3)
-                res[cname].append(timeit(fn))
+                with tuned({1: k1, 3: k3}):
+                    res[cname].append(timeit(fn))
         best = min(res, key=lambda c: min(res[c]))
-        lib.x2_tune(2, 4)
-        lib.x2_tune(1, 0); lib.x2_tune(3, 0)
-        ne_auto = timeit(fn)
         k = dict((c[0], c) for c in configs)[best]
-        lib.x2_tune(1, k[1]); lib.x2_tune(3, k[2])
-        ne_best = timeit(fn)
-        lib.x2_tune(2, 0); lib.x2_tune(1, 0); lib.x2_tune(3, 0)
+        with tuned({2: 4}):
+            ne_auto = timeit(fn)
+            with tuned({1: k[1], 3: k[2]}):
+                ne_best = timeit(fn)
         fl = 2.0 * M * N * Kd
         for c in res:
             tot[c] += n * min(res[c])

@@ -4,7 +4,7 @@ import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 K = importlib.import_module("x2-vlm_amd.kernels")
-lib = importlib.import_module("x2-vlm_amd._lib").lib()
+tuned = importlib.import_module("x2-vlm_amd._lib").tuned
 dev = "cuda"
 NSET = 12
 SHAPES = [("vit qkv", 12608, 2304, 768, "bias"), ("vit dqkv", 12608, 768, 2304, "plain"), ("vit dfc1", 12608, 768, 3072, "plain"),
@@ -41,19 +41,17 @@ for name, M, N, Kd, kind in SHAPES:
             K.gemm_nt(As[i], W, out=outs[i])
         else:
             K.gemm_nt(As[i], W, bias=bias, gamma=gamma, resid=resid, out=outs[i])
-    lib.x2_tune(1, 3); lib.x2_tune(3, 5)
     res = {0: 1e9, 1: 1e9, 2: 1e9}
     ref = None
     for rnd in range(3):
         for k in (1, 2, 0):
-            lib.x2_tune(10, k)
-            res[k] = min(res[k], timeit(run))
-            run(0); torch.cuda.synchronize()
+            with tuned({1: 3, 3: 5, 10: k}):
+                res[k] = min(res[k], timeit(run))
+                run(0); torch.cuda.synchronize()
             if ref is None:
                 ref = outs[0].clone()
             else:
                 assert torch.equal(outs[0], ref), (name, k)          # same arithmetic, same order: bit-identical
-    lib.x2_tune(10, 0); lib.x2_tune(1, 0); lib.x2_tune(3, 0)
     fl = 2.0 * M * N * Kd
     print("%-10s M=%6d N=%5d K=%5d %-6s | two-stage %6.1f us %5.0f TF | three-stage %6.1f us %5.0f TF (%+5.1f %%) | + pipelined reads %6.1f us %5.0f TF (%+5.1f %%)" % (
         name, M, N, Kd, kind, res[1], fl / res[1] / 1e6, res[2], fl / res[2] / 1e6, 100 * (res[2] / res[1] - 1), res[0], fl / res[0] / 1e6,

@@ -8,7 +8,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 import torch
 spec = importlib.util.spec_from_file_location("bench_nt256", os.path.join(HERE, "bench_nt256.py"))
 b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
-K, lib, dev = b.K, b.lib, b.dev
+K, tuned, dev = b.K, b.tuned, b.dev
 NSET = 8
 
 
@@ -62,9 +62,8 @@ for name, M, N, Kd, epi, n in b.shapes(which):
     res = {c[0]: 1e9 for c in configs}
     for _ in range(3):
         for cname, k1, k3 in configs:
-            lib.x2_tune(1, k1); lib.x2_tune(3, k3)
-            res[cname] = min(res[cname], timeit(fn))
-    lib.x2_tune(1, 0); lib.x2_tune(3, 0)
+            with tuned({1: k1, 3: k3}):
+                res[cname] = min(res[cname], timeit(fn))
     best = min(res, key=res.get)
     for c in res:
         tot[c] += n * res[c]

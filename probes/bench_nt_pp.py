@@ -6,7 +6,7 @@ import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 K = importlib.import_module("x2-vlm_amd.kernels")
-lib = importlib.import_module("x2-vlm_amd._lib").lib()
+tuned = importlib.import_module("x2-vlm_amd._lib").tuned
 dev = "cuda"
 NSET = 8
 HEIGHTS = [int(x) for x in (sys.argv[1].split(",") if len(sys.argv) > 1 else "4,5,6".split(","))]
@@ -48,42 +48,35 @@ for name, M, N, Kd, kind in SHAPES:
     resid = torch.randn(M, N, device=dev) if f32 else None
     aux = torch.randn(M, N, device=dev).bfloat16() if kind in ("gelu", "dgelu") else None
 
-    BLOCKED = bool(os.environ.get("PP_BLOCKED"))      # hand the ping-pong kernel A as [K / 64][M][64] (x2_tune(4, 1)): 20 KB of contiguous bytes per tile and step
-    Ab = [a_.view(M, Kd // 64, 64).permute(1, 0, 2).contiguous().view(M, Kd) for a_ in As] if BLOCKED else None
-    cur = {"v": 0}
-
-    As_n = As
-
     def run(i):
-        As_ = Ab if (BLOCKED and cur["v"] != 0) else As_n
         if kind == "bias":
-            K.gemm_nt(As_[i], W, bias=bias, out=outs[i])
+            K.gemm_nt(As[i], W, bias=bias, out=outs[i])
         elif kind == "plain":
-            K.gemm_nt(As_[i], W, out=outs[i])
+            K.gemm_nt(As[i], W, out=outs[i])
         elif kind == "gelu":
-            K.gemm_nt(As_[i], W, bias=bias, aux=aux, act=1, out=outs[i])
+            K.gemm_nt(As[i], W, bias=bias, aux=aux, act=1, out=outs[i])
         elif kind == "dgelu":
-            K.gemm_nt(As_[i], W, aux=aux, act=2, out=outs[i])
+            K.gemm_nt(As[i], W, aux=aux, act=2, out=outs[i])
         elif kind == "resid":
-            K.gemm_nt(As_[i], W, bias=bias, resid=resid, out=outs[i])
+            K.gemm_nt(As[i], W, bias=bias, resid=resid, out=outs[i])
         else:
-            K.gemm_nt(As_[i], W, bias=bias, gamma=gamma, resid=resid, out=outs[i])
+            K.gemm_nt(As[i], W, bias=bias, gamma=gamma, resid=resid, out=outs[i])
     variants = [0] + HEIGHTS
     res = {v: 1e9 for v in variants}
     ref = None
     err = {}
     for rnd in range(3):
         for v in variants:
-            lib.x2_tune(15, v)
-            res[v] = min(res[v], timeit(run))
+            with tuned({15: v}):
+                res[v] = min(res[v], timeit(run))
+                if rnd == 0:
+                    run(0); torch.cuda.synchronize()
             if rnd == 0:
-                run(0); torch.cuda.synchronize()
                 if v == 0:
                     ref = outs[0].float().clone()
                 else:
                     d = (outs[0].float() - ref).abs().max().item()
                     err[v] = d / (ref.abs().max().item() + 1e-9)
-    lib.x2_tune(15, 0)
     fl = 2.0 * M * N * Kd
     line = "%-10s M=%6d N=%5d K=%5d %-6s | auto %6.1f us %5.0f TF" % (name, M, N, Kd, kind, res[0], fl / res[0] / 1e6)
     for v in HEIGHTS:
@@ -95,8 +88,7 @@ M, N, Kd = 1000, 520, 768          # ragged M, N not a multiple of 256
 A = torch.randn(M, Kd, device=dev).bfloat16(); W = (torch.randn(N, Kd, device=dev) / Kd ** 0.5).bfloat16(); b = torch.randn(N, device=dev)
 want = A.float() @ W.float().t() + b
 for v in HEIGHTS:
-    lib.x2_tune(15, v)
-    got = K.gemm_nt(A, W, bias=b, out_dtype=torch.float32)
-    torch.cuda.synchronize()
+    with tuned({15: v}):
+        got = K.gemm_nt(A, W, bias=b, out_dtype=torch.float32)
+        torch.cuda.synchronize()
     print("ragged %dx%dx%d height %d: max |err| vs fp32 matmul %.3e" % (M, N, Kd, v * 32, (got - want).abs().max().item()))
-lib.x2_tune(15, 0)

@@ -4,7 +4,7 @@ import importlib, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 K = importlib.import_module("x2-vlm_amd.kernels")
-lib = importlib.import_module("x2-vlm_amd._lib").lib()
+tuned = importlib.import_module("x2-vlm_amd._lib").tuned
 dev = "cuda"
 
 
@@ -33,9 +33,8 @@ for name, probs in CASES:
     res = {}
     for rep in range(3):
         for knob, split in ((1, 1), (2, 0), (2, 1), (2, 2), (2, 3)):
-            lib.x2_tune(5, knob)
-            t = timeit(lambda: K.gemm_tn_grouped(ps, split=split))
+            with tuned({5: knob}):
+                t = timeit(lambda: K.gemm_tn_grouped(ps, split=split))
             res.setdefault((knob, split), []).append(t)
-    lib.x2_tune(5, 0)
     print("%-12s " % name + "  ".join("%s/s%d %6.1fus %4.0fTF" % ("128" if k == 1 else "256", sp, min(v), fl / min(v) / 1e6)
                                       for (k, sp), v in res.items()))

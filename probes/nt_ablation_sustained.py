@@ -6,6 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 K = importlib.import_module("x2-vlm_amd.kernels")
 lib = importlib.import_module("x2-vlm_amd._lib").lib()
+tuned = importlib.import_module("x2-vlm_amd._lib").tuned
 assert hasattr(lib, "x2_probe_set_buffer"), "needs the probe build"
 dev = "cuda"
 NSET = 8
@@ -32,14 +33,9 @@ for name, M, N, Kd in SHAPES:
     outs = [torch.empty(M, N, device=dev, dtype=torch.bfloat16) for _ in range(NSET)]
     print("%s M=%d N=%d K=%d: sustained launch time in us (160 x 256 tiles)" % (name, M, N, Kd))
     for kname, setup, extra in (("two-stage 16x16x32", ((1, 3), (10, 1)), 0), ("ping-pong, burst", ((15, 5),), 256), ("ping-pong, spread", ((15, 5),), 0)):
-        for k, v in setup:
-            lib.x2_tune(k, v)
         line = "   %-20s" % kname
         for vname, bits in VARIANTS:
-            assert lib.x2_tune(2, bits | extra) == 0
-            t = min(timeit(lambda i: K.gemm_nt(As[i], W, out=outs[i])) for _ in range(3))
+            with tuned({**dict(setup), 2: bits | extra}):
+                t = min(timeit(lambda i: K.gemm_nt(As[i], W, out=outs[i])) for _ in range(3))
             line += " | %s %5.1f" % (vname, t)
-        lib.x2_tune(2, 0)
-        for k, v in setup:
-            lib.x2_tune(k, 0)
         print(line, flush=True)

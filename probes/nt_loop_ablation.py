@@ -7,6 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 K = importlib.import_module("x2-vlm_amd.kernels")
 lib = importlib.import_module("x2-vlm_amd._lib").lib()
+tuned = importlib.import_module("x2-vlm_amd._lib").tuned
 assert hasattr(lib, "x2_probe_set_buffer"), "needs the probe build"
 lib.x2_probe_set_buffer.argtypes, lib.x2_probe_set_buffer.restype = [ctypes.c_void_p], ctypes.c_int
 dev = "cuda"
@@ -23,30 +24,26 @@ for name, M, N, Kd in SHAPES:
         As = [torch.randn(1, Kd, device=dev).bfloat16().expand(M, Kd) for _ in range(NSET)]
     outs = [torch.empty(M, N, device=dev, dtype=torch.bfloat16) for _ in range(NSET)]
     PP = int(os.environ.get("PP_H", "0"))          # 4 / 5 / 6: the ping-pong kernel at 32 x PP_H rows instead of gemm_nt256_kernel
-    if PP:
-        lib.x2_tune(15, PP)
-    else:
-        lib.x2_tune(1, 3)
+    kernel = {15: PP} if PP else {1: 3}
     nbuf = torch.zeros(4096 * 4, device=dev, dtype=torch.int64)
     res = []
     for vname, bits in VARIANTS:
-        assert lib.x2_tune(2, bits) == 0, lib.x2_last_error()
-        for i in range(NSET):
-            K.gemm_nt(As[i], W, out=outs[i])
-        torch.cuda.synchronize()
-        mains, spans = [], []
-        for rep in range(5):
-            nbuf.zero_()
-            lib.x2_probe_set_buffer(ctypes.c_void_p(nbuf.data_ptr()))
-            K.gemm_nt(As[rep % NSET], W, out=outs[rep % NSET])
+        with tuned({**kernel, 2: bits}):
+            for i in range(NSET):
+                K.gemm_nt(As[i], W, out=outs[i])
             torch.cuda.synchronize()
-            lib.x2_probe_set_buffer(None)
-            t = nbuf.view(-1, 4).cpu().double()
-            t = t[t[:, 3] > 0] / 100.0
-            mains.append(float((t[:, 2] - t[:, 1]).mean()))
-            spans.append(float(t[:, 3].max() - t[:, 0].min()))
+            mains, spans = [], []
+            for rep in range(5):
+                nbuf.zero_()
+                lib.x2_probe_set_buffer(ctypes.c_void_p(nbuf.data_ptr()))
+                K.gemm_nt(As[rep % NSET], W, out=outs[rep % NSET])
+                torch.cuda.synchronize()
+                lib.x2_probe_set_buffer(None)
+                t = nbuf.view(-1, 4).cpu().double()
+                t = t[t[:, 3] > 0] / 100.0
+                mains.append(float((t[:, 2] - t[:, 1]).mean()))
+                spans.append(float(t[:, 3].max() - t[:, 0].min()))
         res.append((vname, min(mains), min(spans)))
-    lib.x2_tune(2, 0); lib.x2_tune(1, 0); lib.x2_tune(15, 0)
     steps = Kd // 64
     print("%-10s M=%d N=%d K=%d (%d contraction steps per tile; MFMA issue alone = %.2f us per step at 2.4 GHz)" % (name, M, N, Kd, steps, 1280 / 2400.0))
     for vname, m, sp in res:

@@ -9,6 +9,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 K = importlib.import_module("x2-vlm_amd.kernels")
 lib = importlib.import_module("x2-vlm_amd._lib").lib()
+importlib.import_module("x2-vlm_amd._lib").set_tune(1, 3)     # the whole run: always the 256-column kernel; tile height from its plan
 assert hasattr(lib, "x2_probe_set_buffer"), "needs the probe build: X2VLM_HIP_LIB=probes/_probe/libx2vlm_hip_probe.so"
 lib.x2_probe_set_buffer.argtypes, lib.x2_probe_set_buffer.restype = [ctypes.c_void_p], ctypes.c_int
 dev = "cuda"
@@ -37,7 +38,6 @@ for name, M, N, Kd, kind in SHAPES:
     outs = [torch.empty(M, N, device=dev, dtype=torch.float32 if f32 else torch.bfloat16) for _ in range(NSET)]
     extra = dict(bias=torch.randn(N, device=dev), gamma=torch.rand(N, device=dev), resid=torch.randn(M, N, device=dev) if f32 else None,
                  aux=torch.empty(M, N, device=dev, dtype=torch.bfloat16) if kind == "gelu" else None)
-    lib.x2_tune(1, 3)                       # always the 256-column kernel; tile height from its plan
     nbuf = torch.zeros(4096 * 4, device=dev, dtype=torch.int64)
     for i in range(NSET):
         launch(kind, As[i], W, outs[i], extra)
@@ -54,7 +54,6 @@ for name, M, N, Kd, kind in SHAPES:
         t0 = t[:, 0].min()
         rows.append((t.shape[0], (t[:, 1] - t[:, 0]), (t[:, 2] - t[:, 1]), (t[:, 3] - t[:, 2]), float(t[:, 3].max() - t0),
                      float((t[:, 0] - t0).quantile(0.9))))
-    lib.x2_tune(1, 0)
     n = rows[0][0]
     pro = torch.cat([r[1] for r in rows[1:]]); main = torch.cat([r[2] for r in rows[1:]]); epi = torch.cat([r[3] for r in rows[1:]])
     span = sum(r[4] for r in rows[1:]) / len(rows[1:])

@@ -49,9 +49,8 @@ def cfg(side=True, overlap=True, hold=False):
     return f
 
 
-lib = importlib.import_module("x2-vlm_amd._lib").lib()
 if len(sys.argv) > 2:
-    lib.x2_tune(5, int(sys.argv[2]))
+    importlib.import_module("x2-vlm_amd._lib").set_tune(5, int(sys.argv[2]))       # for the whole run
     print("x2_tune(5, %s)" % sys.argv[2])
 cfg(False, False)()
 REF = step()

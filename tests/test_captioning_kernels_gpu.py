@@ -7,29 +7,13 @@ Tolerances (relative to each tensor's max-abs): bf16 attention outputs and gradi
 MFMA, as in test_kernels_gpu.py); fp32 embedding sums 1e-6; the smoothed loss 1e-6 relative [measured worst 3.6e-8] - tight enough to see the z_ign term, whose ignored column carries a large bias
 here; its bf16 logit gradient 6e-3 of max-abs [3.3e-3], plus two checks the smoothing mass dominates: the sum of a row's gradient over the
 columns that are neither the label nor the ignored id, 1e-2 of ls x the row scale, and the ignored column element-wise."""
-import importlib
-
 import pytest
 import torch
 
+from kernel_helpers import K, relerr, rnd  # noqa: F401 (fixtures)
+
 pytestmark = pytest.mark.gpu
 dev = "cuda"
-
-
-@pytest.fixture(scope="module")
-def K():
-    return importlib.import_module("x2-vlm_amd.kernels")
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
-
-
-def relerr(got, ref):
-    got = got.detach().float().cpu().double()
-    ref = ref.detach().double()
-    return float((got - ref).abs().max() / ref.abs().max().clamp_min(1e-12))
 
 
 def tril_mask(B, L):

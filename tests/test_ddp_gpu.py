@@ -22,6 +22,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from cases import CASES, model_config
+from ddp_helpers import _compare
 
 pytestmark = pytest.mark.gpu
 
@@ -110,24 +111,6 @@ def _oracle_ddp(synthetic, c, world, shift):
             if t.grad is not None:
                 avg[k] = avg.get(k, 0) + t.grad.detach().clone() / world
     return avg, losses
-
-
-def _compare(got, want, what, etol=8e-2):
-    total = float(torch.sqrt(sum((g.double() ** 2).sum() for g in want.values())))
-    bad = []
-    for name, ref in want.items():
-        if name == "text_encoder.cls.predictions.decoder.weight" or name not in got:
-            continue
-        g = got[name].double()
-        ref = ref.double()
-        nerr = abs(float(g.norm()) - float(ref.norm())) / max(float(ref.norm()), 1e-2 * total)
-        eerr = float((g - ref).abs().max()) / max(float(ref.abs().max()), 1e-2 * total / max(ref.numel(), 1) ** 0.5)
-        if nerr > 3e-2 or eerr > etol:
-            bad.append((name, nerr, eerr))
-    missing = [n for n in want if n not in got and n != "text_encoder.cls.predictions.decoder.weight"
-               and float(want[n].abs().max()) > 0]
-    assert not missing, "%s: no gradient for %s" % (what, missing[:5])
-    assert not bad, "%s: %d tensors out of tolerance, worst %s" % (what, len(bad), sorted(bad, key=lambda b: -b[2])[:5])
 
 
 @pytest.mark.parametrize("case", ["tiny", "base_shallow"])

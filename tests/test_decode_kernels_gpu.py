@@ -12,23 +12,16 @@ import importlib
 import pytest
 import torch
 
+from kernel_helpers import K, rnd  # noqa: F401 (fixtures)
+
 pytestmark = pytest.mark.gpu
 dev = "cuda"
 BF16 = torch.bfloat16
 
 
 @pytest.fixture(scope="module")
-def K():
-    return importlib.import_module("x2-vlm_amd.kernels")
-
-
-@pytest.fixture(scope="module")
 def D():
     return importlib.import_module("x2-vlm_amd.decode")
-
-
-def rnd(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
 
 
 def ref_decode(qkv, cache, S, H, n_new, hist, scale):

@@ -20,16 +20,11 @@ import importlib
 import pytest
 import torch
 
-from test_kernels_gpu import bf, relerr, rnd, rowerr, slice_relerr
+from kernel_helpers import K, bf, nt_tile, nt_tile128, relerr, rnd, rowerr, slice_relerr, tuned  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
 TOL_OUT, TOL_GRAD = 8e-3, 1.5e-2
-
-
-@pytest.fixture(scope="module")
-def K():
-    return importlib.import_module("x2-vlm_amd.kernels")
 
 
 def _lib():
@@ -172,13 +167,9 @@ def run_both_forms(case, spec, ref, form, label):
     assert_within(errs, label)
     worst.update(errs)
     if form == 2:
-        lib = _lib()
-        lib.x2_tune(14, 1)
-        try:
+        with tuned({14: 1}):
             assert case.backward(spec, fwd, ask_form=True) == 0, label
             errs = case.backward_errors(ref, case.backward(spec, fwd))
-        finally:
-            lib.x2_tune(14, 0)
         assert_within(errs, label + " as the pair")
         worst = {n: max(e, errs.get(n, 0.0)) for n, e in worst.items()}
     return worst, fwd, got
@@ -258,9 +249,7 @@ def test_attention_dropout_phase_split_gives_the_same_bits(K, name):
     masks regenerated in each: own K/V (form 0 by default) and rows sharing K/V (the pair under x2_tune(14, 1))."""
     case = make_case(K, name, seed=2100)
     spec = K.dropout_spec(0.1, 777, 3)
-    lib = _lib()
-    lib.x2_tune(14, 1)
-    try:
+    with tuned({14: 1}):
         fwd = case.forward(spec)
         assert case.backward(spec, fwd, ask_form=True) == 0
         dq, dk, dv, delta, dS = case.backward(spec, fwd)
@@ -270,8 +259,6 @@ def test_attention_dropout_phase_split_gives_the_same_bits(K, name):
         assert dS is None or torch.equal(dS1, dS)
         case.backward(spec, fwd, phase=2, into=into)
         assert torch.equal(into[1], dk) and torch.equal(into[2], dv) and torch.equal(into[3], delta) and torch.equal(into[0], dq)
-    finally:
-        lib.x2_tune(14, 0)
     assert_within(case.backward_errors(case.reference_for(spec), (dq, dk, dv, delta, dS)), name)
 
 
@@ -317,32 +304,6 @@ def test_attention_dropout_gate_has_teeth(K, name):
 
 
 # ------------------------------------------------------------------------------------------------ NT GEMM epilogue
-
-NT_TILES = [(1, 1, 0), (1, 2, 0), (1, 3, 0), (1, 4, 0), (3, 8, 0), (3, 7, 0), (3, 6, 0), (3, 5, 0), (0, 0, 3), (0, 0, 4), (0, 0, 5), (0, 0, 6)]
-NT_IDS = ["tile128x128", "tile192x128", "tile64x128", "tile160x128", "nt256x256", "nt224x256", "nt192x256", "nt160x256",
-          "pingpong96x256", "pingpong128x256", "pingpong160x256", "pingpong192x256"]
-
-
-def _pin_tile(param):
-    lib = _lib()
-    lib.x2_tune(1, param[0])
-    lib.x2_tune(3, param[1])
-    lib.x2_tune(15, param[2])           # the ping-pong kernel at 32 x value rows
-    yield param
-    lib.x2_tune(1, 0)
-    lib.x2_tune(3, 0)
-    lib.x2_tune(15, 0)
-
-
-@pytest.fixture(params=NT_TILES, ids=NT_IDS)
-def nt_tile(request):
-    yield from _pin_tile(request.param)
-
-
-@pytest.fixture(params=NT_TILES[:4], ids=NT_IDS[:4])
-def nt_tile128(request):
-    yield from _pin_tile(request.param)
-
 
 # (161, 264, 64): one row past a 160-row tile, 8 columns past a 256-column tile
 GEMM_SHAPES = [(300, 200, 192), (161, 264, 64), (97, 136, 128)]

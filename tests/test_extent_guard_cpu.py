@@ -1,10 +1,10 @@
-"""The guard helper of tests/test_kernel_extents_gpu.py on CPU tensors: an untouched buffer passes; a one-element write immediately before or after
+"""The guard helper of tests/test_kernel_extents_gpu.py (tests/kernel_helpers.py) on CPU tensors: an untouched buffer passes; a one-element write immediately before or after
 the interior, in a row gap, in a batch gap or at the last element of the trailing guard fails and is named (region, row, column) - for every dtype,
 also when the written value is itself a NaN with another payload (the comparison is on the bits)."""
 import pytest
 import torch
 
-from test_kernel_extents_gpu import BF16, F32, I32, I64, LEAD, SENTINEL, TALLEST_TILE, _INT_OF, guarded
+from kernel_helpers import BF16, F32, I32, I64, LEAD, SENTINEL, TALLEST_TILE, _INT_OF, guarded
 
 B, L, N, LD, BS = 3, 5, 8, 12, 7      # rows of 8 inside 12, batches of 5 rows inside 7
 

@@ -39,85 +39,11 @@ import math
 import pytest
 import torch
 
+from kernel_helpers import (BF16, F32, I32, I64, NT_IDS, NT_TILES, SENTINEL, _ALIVE, _INT_OF, K, bf, filled, guarded, lib,  # noqa: F401 (fixtures)
+                            nt_pinned, relerr, rnd, tn_tile, tuned)
+
 pytestmark = pytest.mark.gpu
 dev = "cuda"
-BF16, F32, I32, I64 = torch.bfloat16, torch.float32, torch.int32, torch.int64
-
-# ------------------------------------------------------------------------------------------------ the guard helper (CPU-testable)
-# sentinel bit patterns: NaNs with a payload for the float types (as the integer of the same width), fixed negative values for the integer types
-_INT_OF = {F32: I32, BF16: torch.int16, I32: I32, I64: I64}
-SENTINEL = {F32: 0x7FC5A5A5, BF16: 0x7FC5, I32: -0x5A5A5A5B, I64: -0x5A5A5A5A5A5A5A5B}
-LEAD = 4096
-TALLEST_TILE = 256
-_ALIVE = []          # every allocation of the running test: a temporary handed to a launch as a bare pointer must not be recycled for the next one
-
-
-class Guard:
-    """checker of one guarded allocation: __call__ asserts that every element outside the interior still holds the sentinel bits"""
-
-    def __init__(self, ints, pattern, lead, shape3, ld, bs, name):
-        self.ints, self.pattern, self.lead, self.shape3, self.ld, self.bs, self.name = ints, pattern, lead, shape3, ld, bs, name
-        B, L, N = shape3
-        self.span = ((B - 1) * bs + L - 1) * ld + N
-        rel = torch.arange(self.span, device=ints.device)
-        row, col = rel // ld, rel % ld
-        inside = (col < N) & (row % bs < L)
-        self.outside = torch.ones(ints.numel(), dtype=torch.bool, device=ints.device)
-        self.outside[lead:lead + self.span] = ~inside
-
-    def bad(self):
-        """None, or (region, row, column) of the first element outside the interior that lost the pattern; row / column count from the interior's
-        first element in units of ld (negative rows: the leading guard)"""
-        wrong = (self.ints != self.pattern) & self.outside
-        if not bool(wrong.any()):
-            return None
-        off = int(torch.nonzero(wrong)[0])
-        rel = off - self.lead
-        row, col = rel // self.ld, rel % self.ld
-        if rel < 0:
-            region = "lead"
-        elif rel >= self.span:
-            region = "tail"
-        elif col >= self.shape3[2]:
-            region = "row gap"
-        else:
-            region = "batch gap"
-        return region, row, col
-
-    def __call__(self):
-        b = self.bad()
-        assert b is None, "%s: write outside the extent: region %s, row %d, column %d" % ((self.name,) + b)
-
-
-def guarded(shape, dtype, ld=None, batch_stride=None, lead=LEAD, tail=None, device=dev, name="buffer"):
-    """One flat allocation filled with the dtype's sentinel bit pattern -> (interior view of `shape`, Guard).
-    shape (n,), (rows, N) or (B, L, N); rows are ld >= N elements apart, batches batch_stride >= L rows apart.  tail: elements behind the interior
-    (default and minimum for 2-D / 3-D: 256 rows x ld - the tallest tile of any kernel; for a 1-D workspace the caller passes one more unit of its
-    layout); lead and tail are never below 4096 elements."""
-    shape = tuple(shape)
-    shape3 = (1,) * (3 - len(shape)) + shape
-    B, L, N = shape3
-    ld = N if ld is None else ld
-    bs = L if batch_stride is None else batch_stride
-    assert ld >= N and bs >= L and lead >= LEAD
-    floor = LEAD if len(shape) == 1 else max(LEAD, TALLEST_TILE * ld)
-    tail = floor if tail is None else max(tail, floor)
-    span = ((B - 1) * bs + L - 1) * ld + N
-    it = _INT_OF[dtype]
-    ints = torch.full((lead + span + tail,), SENTINEL[dtype], dtype=it, device=device)
-    _ALIVE.append(ints)
-    flat = ints.view(dtype)
-    strides = (bs * ld, ld, 1)[3 - len(shape):]
-    view = torch.as_strided(flat, shape, strides, lead)
-    return view, Guard(ints, SENTINEL[dtype], lead, shape3, ld, bs, name)
-
-
-def filled(t, **kw):
-    """a guarded copy of host tensor t on the device (inputs: everything around the values is NaN / the integer sentinel) -> view"""
-    v, _ = guarded(t.shape, t.dtype, **kw)
-    v.copy_(t)
-    return v
-
 
 # ------------------------------------------------------------------------------------------------ fixtures, references
 
@@ -127,32 +53,6 @@ def _release_allocations():
     if _ALIVE and _ALIVE[0].is_cuda:
         torch.cuda.synchronize()
     del _ALIVE[:]
-
-
-@pytest.fixture(scope="module")
-def K():
-    return importlib.import_module("x2-vlm_amd.kernels")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return importlib.import_module("x2-vlm_amd._lib").lib()
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
-
-
-def bf(t):
-    return t.to(BF16)
-
-
-def relerr(got, ref):
-    got = got.detach().float().cpu().double()
-    ref = ref.detach().double()
-    assert bool(torch.isfinite(got).all()), "non-finite result"
-    return float((got - ref).abs().max() / ref.abs().max().clamp_min(1e-12))
 
 
 def gelu64(x):
@@ -195,18 +95,10 @@ def test_guard_reports_a_workspace_one_partial_row_short(K):
 
 # ------------------------------------------------------------------------------------------------ 2. GEMMs
 
-NT_TILES = [(0, 0, 0), (1, 1, 0), (1, 2, 0), (1, 3, 0), (1, 4, 0), (3, 8, 0), (3, 7, 0), (3, 6, 0), (3, 5, 0), (0, 0, 3), (0, 0, 4), (0, 0, 5), (0, 0, 6)]
-NT_IDS = ["auto", "tile128x128", "tile192x128", "tile64x128", "tile160x128", "nt256x256", "nt224x256", "nt192x256", "nt160x256", "pingpong96x256",
-          "pingpong128x256", "pingpong160x256", "pingpong192x256"]
-
-
-@pytest.fixture(params=NT_TILES, ids=NT_IDS)
-def nt_tile(request, lib):
-    lib.x2_tune(1, request.param[0]); lib.x2_tune(3, request.param[1]); lib.x2_tune(15, request.param[2])
-    try:
+@pytest.fixture(params=[(0, 0, 0)] + NT_TILES, ids=["auto"] + NT_IDS)
+def nt_tile(request):
+    with nt_pinned(request.param):
         yield request.param
-    finally:
-        lib.x2_tune(1, 0); lib.x2_tune(3, 0); lib.x2_tune(15, 0)
 
 
 _NT_REF = {}
@@ -262,8 +154,7 @@ def test_gemm_nt_extents(K, nt_tile, M, N, Kd):
 def test_gemm_nt_dgelu_colparts_extents(K, lib, M, N, Kd, tile):
     Ad, Bd, _, _, pred, _, _, pre, ref = nt_operands(M, N, Kd)
     rows = 2 * ceil_div(M, 64)
-    lib.x2_tune(1, 1); lib.x2_tune(3, tile)
-    try:
+    with tuned({1: 1, 3: tile}):
         Cv, gC = guarded((M, N), BF16, ld=N + 8, name="C")
         parts, gP = guarded((rows * N,), F32, tail=2 * N, name="colparts")
         nrows = C.c_int(-1)
@@ -278,8 +169,6 @@ def test_gemm_nt_dgelu_colparts_extents(K, lib, M, N, Kd, tile):
         all_ok(gS, gP)
         # the partial rows sum the fp32 values before their bf16 rounding: the project's fp32 bound against the column's absolute sum
         assert float((cs.cpu().double() - 3.0 - want.sum(0)).abs().max()) <= 1e-5 * float(want.abs().sum(0).max()) + 1e-6
-    finally:
-        lib.x2_tune(1, 0); lib.x2_tune(3, 0)
 
 
 def test_gemm_nt_splitk_extents(K):
@@ -295,15 +184,6 @@ def test_gemm_nt_splitk_extents(K):
         assert relerr(Cv, ref) < 1e-5, (M, N, Kd, slices, room)
         if room <= 1:      # nothing passes through a workspace that holds fewer than two slices
             assert bool((ws.view(I32) == SENTINEL[F32]).all())
-
-
-@pytest.fixture(params=[1, 2], ids=["tn128x128", "tn256x256"])
-def tn_tile(request, lib):
-    lib.x2_tune(5, request.param)
-    try:
-        yield request.param
-    finally:
-        lib.x2_tune(5, 0)
 
 
 def tn_problem(Mc, N, Kd, seed):
@@ -585,11 +465,8 @@ def test_attention_extents(K, lib, name):
 
 @pytest.mark.parametrize("name", ONE_PASS)
 def test_attention_extents_two_kernels_where_one_pass_applies(K, lib, name):
-    lib.x2_tune(14, 1)
-    try:
+    with tuned({14: 1}):
         run_attention_extents(K, lib, **ATTN_GEOMETRIES[name])
-    finally:
-        lib.x2_tune(14, 0)
 
 
 @pytest.mark.parametrize("name", ["long209", "long272"])
@@ -654,9 +531,8 @@ def ln_case(rows, D, period, seed):
 def test_layernorm_fwd_extents(K, lib, rows, D, period):
     total, x, w, b, sel, skip, mu, rs, y = ln_case(rows, D, period, seed=rows * D)
     xd, wd, bd = filled(x), filled(w), filled(b)
-    try:
-        for knob in (1, 2, 4, 0):
-            lib.x2_tune(13, knob)
+    for knob in (1, 2, 4, 0):
+        with tuned({13: knob}):
             (yb, gB), (yf, gF) = guarded((total, D), BF16, name="y_bf16"), guarded((total, D), F32, name="y_f32")
             (mean, gM), (rstd, gR) = guarded((rows,), F32, tail=rows, name="mean"), guarded((rows,), F32, tail=rows, name="rstd")
             K.call("x2_layernorm_fwd", K.ptr(xd), K.ptr(wd), K.ptr(bd), K.ptr(yb), K.ptr(yf), K.ptr(mean), K.ptr(rstd), rows, D, 1e-6, period, 0, 0, 1.0, None)
@@ -664,8 +540,6 @@ def test_layernorm_fwd_extents(K, lib, rows, D, period):
             assert relerr(yf[sel.to(dev)], y) < 1e-5 and relerr(yb[sel.to(dev)], y) < 6e-3, knob
             assert relerr(mean, mu) < 1e-5 and relerr(rstd, rs) < 1e-5, knob
             assert untouched(yb, skip.to(dev)) and untouched(yf, skip.to(dev)), knob      # the cls rows (and the rows past the last one) are not written
-    finally:
-        lib.x2_tune(13, 0)
 
 
 @pytest.mark.parametrize("defer", [0, 1])
@@ -1205,9 +1079,8 @@ def test_wrapper_workspaces_of_the_gemms(K, lib, exact_workspace):
     Mc, N, Kd = 192, 264, 320
     dY, X = bf(rnd(Mc, N, seed=1)), bf(rnd(Mc, Kd, seed=2))
     ref = dY.double().t() @ X.double()
-    try:
-        for tile in (0, 1, 2):
-            lib.x2_tune(5, tile)
+    for tile in (0, 1, 2):
+        with tuned({5: tile}):
             for split in (0, 1, 2, 3):
                 if split > 1 and tile == 1:
                     continue                      # the 128x128 kernel adds split partials atomically
@@ -1217,8 +1090,6 @@ def test_wrapper_workspaces_of_the_gemms(K, lib, exact_workspace):
                 all_ok(*(g for _, g, _ in exact_workspace))
                 assert relerr(dW, ref) < 1e-5, (tile, split)
                 assert split == 1 or exact_workspace[-1][2] == (split if split else 4) * 4 * 65536
-    finally:
-        lib.x2_tune(5, 0)
     # linear_f32 with K slices: ksplit * M * N
     a, b, bias = rnd(33, 200, seed=1), rnd(10, 200, seed=2), rnd(10, seed=3)
     del exact_workspace[:]

@@ -6,26 +6,14 @@ head biases.
 References are float64 on the CPU after the kernels' own input rounding (bf16 inputs rounded first), as in test_kernels_gpu.py;
 where a kernel claims bit-identical outputs across its variants, the test asserts bit equality.  Besides the whole-tensor bound,
 LayerNorm outputs are bounded row by row against each row's own reference max-abs (`rowerr`)."""
-import importlib
-
 import pytest
 import torch
 
-from test_kernels_gpu import bf, relerr, rnd, rowerr
+from kernel_helpers import K, bf, relerr, rnd, rowerr, tuned  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
 EPS = 1e-6
-
-
-@pytest.fixture(scope="module")
-def K():
-    return importlib.import_module("x2-vlm_amd.kernels")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return importlib.import_module("x2-vlm_amd._lib").lib()
 
 
 def ln64(x, w, b, eps=EPS):
@@ -53,7 +41,7 @@ def element_index(sel, D):
 
 @pytest.mark.parametrize("rows,period", [(8191, 0), (8192, 0), (42 * 196, 196)], ids=["8191", "8192", "8232p196"])
 @pytest.mark.parametrize("D", [128, 512, 768, 1000, 1024, 2048], ids=["nv1", "nv2", "nv3", "nv4ragged", "nv4", "nv8"])
-def test_layernorm_fwd_rows_per_wave(K, lib, rows, period, D):
+def test_layernorm_fwd_rows_per_wave(K, rows, period, D):
     """x2_tune(13, v): one row per wave (layernorm_fwd_kernel<NV>) and 2 / 4 rows per wave (layernorm_fwd_rows_kernel<NV, RPW>; D > 1024
     always takes one row) and the automatic choice (2 from 8192 rows on): same arithmetic, same summation order, so y (fp32, bf16),
     mean and rstd are bit-identical across the forms and match float64; 8191 rows leave the last wave of every RPW form partial.
@@ -64,13 +52,10 @@ def test_layernorm_fwd_rows_per_wave(K, lib, rows, period, D):
     keep = K.dropout_keep(spec, element_index(sel, D)).double()
     xd, wd, bd = x.to(dev), w.to(dev), b.to(dev)
     outs, drops = {}, {}
-    try:
-        for v in (1, 2, 4, 0):
-            lib.x2_tune(13, v)
+    for v in (1, 2, 4, 0):
+        with tuned({13: v}):
             outs[v] = K.layernorm_fwd(xd, wd, bd, EPS, rows=rows, period=period, want_f32=True)
             drops[v] = K.layernorm_fwd(xd, wd, bd, EPS, rows=rows, period=period, want_f32=True, drop=spec)
-    finally:
-        lib.x2_tune(13, 0)
     selg = sel.to(dev)
     for v in (2, 4, 0):
         for a_, b_ in zip(outs[v], outs[1]):

@@ -16,58 +16,10 @@ import pytest
 import torch
 
 from oracle import x2vlm_oracle as O
+from kernel_helpers import K, bf, nt_tile, relerr, rnd, rowerr, slice_relerr, tn_tile, tuned  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
-
-
-@pytest.fixture(scope="module")
-def K():
-    return importlib.import_module("x2-vlm_amd.kernels")
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
-
-
-def bf(t):
-    return t.to(torch.bfloat16)
-
-
-def relerr(got, ref):
-    got = got.detach().float().cpu().double()
-    ref = ref.detach().double()
-    return float((got - ref).abs().max() / ref.abs().max().clamp_min(1e-12))
-
-
-def slice_relerr(got, ref, floor=1e-3):
-    """relerr of every slice along dim 0 (a row, a (sequence, head) block) against that slice's own reference max-abs, floored at
-    `floor` x the tensor's max-abs so that a slice of (near) zeros is held to the tensor's scale instead of dividing by ~0: a
-    wrong row or head cannot hide behind a larger one elsewhere in the tensor"""
-    got = got.detach().float().cpu().double().reshape(ref.shape[0], -1)
-    ref = ref.detach().double().reshape(ref.shape[0], -1)
-    den = ref.abs().amax(1).clamp_min(floor * float(ref.abs().max())).clamp_min(1e-30)
-    return float(((got - ref).abs().amax(1) / den).max())
-
-
-def rowerr(got, ref):
-    """slice_relerr of a [rows, D] tensor, row by row"""
-    return slice_relerr(got, ref)
-
-
-@pytest.fixture(params=[(1, 1, 0), (1, 2, 0), (1, 3, 0), (1, 4, 0), (3, 8, 0), (3, 7, 0), (3, 6, 0), (3, 5, 0), (0, 0, 3), (0, 0, 4), (0, 0, 5), (0, 0, 6)],
-                ids=["tile128x128", "tile192x128", "tile64x128", "tile160x128", "nt256x256", "nt224x256", "nt192x256", "nt160x256",
-                     "pingpong96x256", "pingpong128x256", "pingpong160x256", "pingpong192x256"])
-def nt_tile(request):
-    lib = importlib.import_module("x2-vlm_amd._lib").lib()
-    lib.x2_tune(1, request.param[0])
-    lib.x2_tune(3, request.param[1])
-    lib.x2_tune(15, request.param[2])           # the ping-pong kernel (32x32x16 MFMAs) at 32 x value rows; runs the same tests as every other tile
-    yield request.param
-    lib.x2_tune(1, 0)
-    lib.x2_tune(3, 0)
-    lib.x2_tune(15, 0)
 
 
 @pytest.mark.parametrize("M,N,K_", [(256, 256, 128), (300, 200, 192), (788, 2304, 768), (12608, 768, 768), (100, 30528, 64)])
@@ -119,11 +71,9 @@ def test_gemm_nt_plain_and_epilogues(K, M, N, K_, nt_tile):
 def test_gemm_nt_dgelu_with_column_sums(K, M, N, K_, tile):
     """x2_gemm_nt_dgelu_colparts (epilogue variant 10): the GELU' input gradient equals the plain variant-3 launch bit for bit
     (same epilogue arithmetic) and the reduced per-wave partial rows equal its column sums; immediate and deferred reduction."""
-    lib = importlib.import_module("x2-vlm_amd._lib").lib()
     A, B = bf(rnd(M, K_, seed=51)).to(dev), bf(rnd(N, K_, seed=52, scale=K_ ** -0.5)).to(dev)
     pre = bf(rnd(M, N, seed=53)).to(dev)
-    lib.x2_tune(1, 1); lib.x2_tune(3, tile)
-    try:
+    with tuned({1: 1, 3: tile}):
         ref = K.gemm_nt(A, B, aux=pre, act=2)
         cs = torch.full((N,), 3.0, device=dev)
         got = K.gemm_nt_dgelu_colsum(A, B, pre, cs)
@@ -144,8 +94,6 @@ def test_gemm_nt_dgelu_with_column_sums(K, M, N, K_, tile):
         finally:
             K.DEFERRED = None
         assert torch.equal(got2, got) and relerr(cs2, (cs - 3.0).cpu()) < 1e-6
-    finally:
-        lib.x2_tune(1, 0); lib.x2_tune(3, 0)
 
 
 @pytest.mark.parametrize("tmw", [8, 7, 6, 5], ids=["nt256x256", "nt224x256", "nt192x256", "nt160x256"])
@@ -154,7 +102,6 @@ def test_gemm_nt_256_column_kernel_matches_the_default_one(K, M, N, K_, tmw):
     """x2_tune(1, 3): the 8-wave 256-column kernel (gemm_nt256_kernel, all four tile heights) shares the epilogue code with the
     128-column kernels, so every compiled feature set - incl. dropout and DropPath row factors, whose masks are functions
     of the element index - must reproduce their outputs up to the order of the fp32 accumulation."""
-    lib = importlib.import_module("x2-vlm_amd._lib").lib()
     A, B = bf(rnd(M, K_, seed=41)).to(dev), bf(rnd(N, K_, seed=42, scale=K_ ** -0.5)).to(dev)
     bias, gamma, resid = rnd(N, seed=43).to(dev), rnd(N, seed=44).to(dev), rnd(M, N, seed=45).to(dev)
     pre = bf(rnd(M, N, seed=46)).to(dev)
@@ -177,17 +124,14 @@ def test_gemm_nt_256_column_kernel_matches_the_default_one(K, M, N, K_, tmw):
             return K.gemm_nt(A, B, bias=bias, gamma=gamma, resid=resid, out_dtype=torch.float32), aux
         return K.gemm_nt(A, B, bias=bias, gamma=gamma, resid=resid, out_dtype=torch.float32, rowscale=rowscale), aux
 
-    try:
-        for kind in ("bias_bf16", "bias_f32", "gelu", "dgelu", "bias_drop_resid", "layerscale", "layerscale_droppath"):
-            lib.x2_tune(1, 1); lib.x2_tune(3, 1)
+    for kind in ("bias_bf16", "bias_f32", "gelu", "dgelu", "bias_drop_resid", "layerscale", "layerscale_droppath"):
+        with tuned({1: 1, 3: 1}):
             ref, ref_aux = run(kind)
-            lib.x2_tune(1, 3); lib.x2_tune(3, tmw)
+        with tuned({1: 3, 3: tmw}):
             got, got_aux = run(kind)
-            for g_, r_ in ((got, ref), (got_aux, ref_aux)):
-                tol = 4e-6 if g_.dtype == torch.float32 else 8e-3
-                assert float((g_.float() - r_.float()).abs().max()) <= tol * max(1.0, float(r_.float().abs().max())), kind
-    finally:
-        lib.x2_tune(1, 0); lib.x2_tune(3, 0)
+        for g_, r_ in ((got, ref), (got_aux, ref_aux)):
+            tol = 4e-6 if g_.dtype == torch.float32 else 8e-3
+            assert float((g_.float() - r_.float()).abs().max()) <= tol * max(1.0, float(r_.float().abs().max())), kind
 
 
 @pytest.mark.parametrize("K_", [64, 128, 192, 256, 320, 768, 3072])
@@ -196,23 +140,18 @@ def test_gemm_nt_160_row_ring_variants_are_bit_identical(K, K_):
     (10, 2) and the shipped one - three stages + the fragment reads of the next step issued behind the current step's last MFMAs
     (10, 0).  Same products in the same order: the outputs must be bit-identical, for every prologue / tail length of the loops
     (1, 2, 3, 4, 5 contraction steps and long ones), ragged M and N, a bf16 and an fp32 + residual epilogue."""
-    lib = importlib.import_module("x2-vlm_amd._lib").lib()
     M, N = 1000, 712
     A, B = bf(rnd(M, K_, seed=51)).to(dev), bf(rnd(N, K_, seed=52, scale=K_ ** -0.5)).to(dev)
     bias, gamma, resid = rnd(N, seed=53).to(dev), rnd(N, seed=54).to(dev), rnd(M, N, seed=55).to(dev)
-    try:
-        lib.x2_tune(1, 3); lib.x2_tune(3, 5)
-        outs = {}
-        for ring in (1, 2, 0):
-            lib.x2_tune(10, ring)
+    outs = {}
+    for ring in (1, 2, 0):
+        with tuned({1: 3, 3: 5, 10: ring}):
             outs[ring] = (K.gemm_nt(A, B, bias=bias), K.gemm_nt(A, B, bias=bias, gamma=gamma, resid=resid, out_dtype=torch.float32))
-        torch.cuda.synchronize()
-        ref = (A.float() @ B.float().t() + bias)
-        assert relerr(outs[1][0], ref.cpu()) < 6e-3
-        for ring in (2, 0):
-            assert torch.equal(outs[ring][0], outs[1][0]) and torch.equal(outs[ring][1], outs[1][1]), ring
-    finally:
-        lib.x2_tune(10, 0); lib.x2_tune(1, 0); lib.x2_tune(3, 0)
+    torch.cuda.synchronize()
+    ref = (A.float() @ B.float().t() + bias)
+    assert relerr(outs[1][0], ref.cpu()) < 6e-3
+    for ring in (2, 0):
+        assert torch.equal(outs[ring][0], outs[1][0]) and torch.equal(outs[ring][1], outs[1][1]), ring
 
 
 @pytest.mark.parametrize("M,N,K_,slices", [(768, 768, 30528, 0), (96, 768, 30528, 0), (40, 256, 4096, 0), (300, 200, 1024, 3),
@@ -281,14 +220,6 @@ def test_gemm_nt_strided_views(K):
     ref = wide[:, Kd:2 * Kd].float().cpu() @ B.float().cpu().t()
     assert relerr(outw[:, 256:], ref) < 6e-3
     assert float(outw[:, :256].abs().max()) == 0.0
-
-
-@pytest.fixture(params=[1, 2], ids=["tn128x128", "tn256x256"])
-def tn_tile(request):
-    lib = importlib.import_module("x2-vlm_amd._lib").lib()
-    lib.x2_tune(5, request.param)        # 1: always the 128x128 kernel, 2: 256x256 whenever the contraction allows
-    yield request.param
-    lib.x2_tune(5, 0)
 
 
 @pytest.mark.parametrize("Mc,N,K_", [(128, 128, 128), (788, 768, 768), (1920, 256, 3072), (12608, 768, 2304), (100, 136, 72),
@@ -450,10 +381,8 @@ def run_attention(K, B, Bkv, H, Lq, Lk, use_bias, use_mask, kv_map, seed, bias_l
     assert form == (1 if kv_map is None and 64 < Lq <= 208 and 64 < Lk <= 208 else 2 if kv_map is not None and Lq <= 128 and Lk <= 208
                     else 3 if long_ok else 0)
     one_pass = form != 0
-    lib = importlib.import_module("x2-vlm_amd._lib").lib()
     if one_pass:
-        lib.x2_tune(14, 1)
-        try:
+        with tuned({14: 1}):
             two = backward()
             check(*two)
             for a_, b_ in zip(got[:3], two[:3]):
@@ -466,8 +395,6 @@ def run_attention(K, B, Bkv, H, Lq, Lk, use_bias, use_mask, kv_map, seed, bias_l
                 if Lkp > Lk:
                     assert float(got[4][..., Lk:].float().abs().max()) == 0.0 and float(two[4][..., Lk:].float().abs().max()) == 0.0
             _phase_split_matches(backward, two)
-        finally:
-            lib.x2_tune(14, 0)
     else:
         _phase_split_matches(backward, got)
 
@@ -529,7 +456,6 @@ def test_attention_one_pass_forms_agree_under_dropout(K):
     """Probability dropout (xbert.py:399) in the shared-K/V one-pass backward: the element index of (sequence, head, query, key) - hence
     the mask - is the one the forward and the two-kernel backward use, so on the same inputs the two backward forms agree to rounding
     (a wrong index would decorrelate the masks: errors of order one).  9 sequences on one image = 3 chunks of 4."""
-    lib = importlib.import_module("x2-vlm_amd._lib").lib()
     d, H, Lq, Lk, kv_map = 64, 3, 30, 70, [0] * 9 + [1] * 2
     B, Bkv = len(kv_map), 2
     qd, dod = (bf(rnd(B * Lq, H * d, seed=600 + i)).to(dev) for i in range(2))
@@ -544,17 +470,14 @@ def test_attention_one_pass_forms_agree_under_dropout(K):
     K.attn_fwd(K.view3(qd, B, Lq), K.view3(kd, Bkv, Lk), K.view3(vd, Bkv, Lk), B, Bkv, H, Lq, Lk, d ** -0.5, K.view3(od, B, Lq), lse,
                **{k_: v_ for k_, v_ in kw.items() if k_ not in ("seq_off", "seq_ids")})
     res = []
-    try:
-        for knob in (0, 1):
-            lib.x2_tune(14, knob)
+    for knob in (0, 1):
+        with tuned({14: knob}):
             dq, dk, dv, delta = torch.full_like(qd, float("nan")), torch.full_like(kd, float("nan")), torch.full_like(vd, float("nan")), torch.empty_like(lse)
             args = (K.view3(qd, B, Lq), K.view3(kd, Bkv, Lk), K.view3(vd, Bkv, Lk), K.view3(od, B, Lq), K.view3(dod, B, Lq), B, Bkv, H, Lq, Lk,
                     d ** -0.5, lse, delta, K.view3(dq, B, Lq), K.view3(dk, Bkv, Lk), K.view3(dv, Bkv, Lk))
             assert K.attn_bwd(*args, ask_form=True, **kw) == (2 if knob == 0 else 0)
             K.attn_bwd(*args, **kw)
             res.append((dq, dk, dv, delta))
-    finally:
-        lib.x2_tune(14, 0)
     for a_, b_ in zip(res[0], res[1]):
         assert bool(torch.isfinite(a_.float()).all()) and relerr(a_.float(), b_.float().cpu()) < 6e-3
 
@@ -595,7 +518,6 @@ def test_attention_long_one_pass_at_the_full_size_of_x2vlm_large(K):
     """BASELINE configs[3] on one GPU: batch 32 x 16 heads x N = 577 (512 workgroups = two rounds of the chip, 84 MB of dQ partials in the workspace,
     the XCD-aware block order over 16 heads): the oracle does not reach this size in test time, so the long one-pass backward is held against the
     dQ + dK/dV pair on the same inputs (the pair against the oracle: test_attention_long_keys) and against itself (two runs, same bits)."""
-    lib = importlib.import_module("x2-vlm_amd._lib").lib()
     B, H, N, d = 32, 16, 577, 64
     HD = H * d
     g_ = torch.Generator().manual_seed(77)
@@ -607,9 +529,8 @@ def test_attention_long_one_pass_at_the_full_size_of_x2vlm_large(K):
     K.attn_fwd(K.view3(qkv, B, N, 0), K.view3(qkv, B, N, HD), K.view3(qkv, B, N, 2 * HD), B, B, H, N, N, d ** -0.5, K.view3(out, B, N), lse,
                bias=bias, bias_log2=True)
     res = []
-    try:
-        for knob in (0, 1, 0):
-            lib.x2_tune(14, knob)
+    for knob in (0, 1, 0):
+        with tuned({14: knob}):
             dqkv = torch.full_like(qkv, float("nan")); delta = torch.full_like(lse, float("nan"))
             dS = torch.zeros(B, H, N, K.round_up(N, 64), device=dev, dtype=torch.bfloat16)
             args = (K.view3(qkv, B, N, 0), K.view3(qkv, B, N, HD), K.view3(qkv, B, N, 2 * HD), K.view3(out, B, N), K.view3(dout, B, N), B, B, H, N, N,
@@ -619,8 +540,6 @@ def test_attention_long_one_pass_at_the_full_size_of_x2vlm_large(K):
             K.attn_bwd(*args, **kw)
             res.append((dqkv, delta, dS.float().sum(0)))
             del dS
-    finally:
-        lib.x2_tune(14, 0)
     one, two, again = res
     assert bool(torch.isfinite(one[0].float()).all()) and bool(torch.isfinite(one[1]).all())
     for j in range(3):            # dQ, dK, dV blocks of the fused gradient

@@ -21,7 +21,7 @@ Worst values observed on MI355X over the four iterations (bound in brackets):
   shipped_1b              0              4.31e-08          7.58e-08    |     1.12e-3        9.11e-3             6.25e-4
   bbox_only_text          0              4.53e-08          6.10e-08    |     1.12e-3        1.40e-2             4.79e-4
   text_video              0              9.52e-08          4.32e-08    |     1.12e-3        9.84e-3             3.82e-4
-  two ranks, losses against the oracle [5e-3]: shipped_1b 1.04e-3, bbox_only_text 1.04e-3; gradients within test_ddp_gpu._compare's bounds.
+  two ranks, losses against the oracle [5e-3]: shipped_1b 1.04e-3, bbox_only_text 1.04e-3; gradients within ddp_helpers._compare's bounds.
 (At these shapes no kernel splits a reduction over atomics: wrapper and eager module agree to fp32 rounding.)
 Under the parent's _publish (equal cotangents taken for the plain sum) shipped_1b and text_video fail bound (a) at every iteration: the region
 gradients arrive at twice their weight - worst per-tensor gradient error 1.0 [5e-3] in both, norm off by 0.452 / 0.552 [2e-3]."""
@@ -380,7 +380,7 @@ def test_two_ranks_unpatched_run_mixed_iter_matches_oracle(name, synthetic):
     two-rank gradients with the bounds of test_two_ranks_replayed_mixed_iteration_matches_oracle.  bbox_only_text: the region part's backward
     is recomputed eagerly and the text part runs eagerly - this rank's own gradients, which backward_step must average, next to fused gradients
     that are averaged already."""
-    from test_ddp_gpu import _compare
+    from ddp_helpers import _compare
     conf = CONFIGS[name]
     world = 2
     mgr = mp.Manager()

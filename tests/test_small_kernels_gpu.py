@@ -14,41 +14,12 @@ import math
 import pytest
 import torch
 
+from kernel_helpers import K, bf, relerr, rnd, slice_relerr  # noqa: F401 (fixtures)
 from oracle import x2vlm_oracle as O
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
 SENT = 7.5            # sentinel: exactly representable, far from every test value's rounding
-
-
-@pytest.fixture(scope="module")
-def K():
-    return importlib.import_module("x2-vlm_amd.kernels")
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
-
-
-def bf(t):
-    return t.to(torch.bfloat16)
-
-
-def relerr(got, ref):
-    got = got.detach().float().cpu().double()
-    ref = ref.detach().double()
-    return float((got - ref).abs().max() / ref.abs().max().clamp_min(1e-12))
-
-
-def slice_relerr(got, ref, floor=1e-3):
-    """relerr of every slice along dim 0 (a row, a chunk) against that slice's own reference max-abs, floored at `floor` x the
-    tensor's max-abs so that a slice of (near) zeros is held to the tensor's scale instead of dividing by ~0: a wrong row cannot
-    hide behind a larger one elsewhere in the tensor"""
-    got = got.detach().float().cpu().double().reshape(ref.shape[0], -1)
-    ref = ref.detach().double().reshape(ref.shape[0], -1)
-    den = ref.abs().amax(1).clamp_min(floor * float(ref.abs().max())).clamp_min(1e-30)
-    return float(((got - ref).abs().amax(1) / den).max())
 
 
 def check(name, got, ref, tol, floor=1e-3):

@@ -13,23 +13,17 @@ running sums, u = 2^-24) - with inputs placed so that float64 scores differ by m
 slots with identical bits per question (lowest slot first); order exact, probabilities within twice the score bound relative plus 1e-7.
 mlm_ce_rows: lse bit-equal to mlm_ce_fwd's, loss_row 0 where the label is -100, its mean over the counted rows mlm_ce_fwd's loss, and
 lse - z[label] of the same bf16 operands in float64 within the fp32 accumulation bound of the Hd-term dot products."""
-import importlib
-
 import numpy as np
 import pytest
 import torch
 
 from cases_vqa import first_stage, second_stage
+from kernel_helpers import K  # noqa: F401 (fixture)
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
 F32, I32, I64 = torch.float32, torch.int32, torch.int64
 CANARY = 8
-
-
-@pytest.fixture(scope="module")
-def K():
-    return importlib.import_module("x2-vlm_amd.kernels")
 
 
 _LOGITS = {}

@@ -4,6 +4,7 @@ The product path has no fallback: if the HIP library is missing or cannot be loa
 raises, and every op of the package fails with it.  Build it with __graft_entry__.build() or
 x2-vlm_amd/csrc/build.sh (hipcc --offload-arch=gfx950).
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -136,10 +137,33 @@ def lib():
         h.x2_attn_bwd_one_pass.argtypes, h.x2_attn_bwd_one_pass.restype = [C.POINTER(AttnArgs)], I
         for kv in filter(None, os.environ.get("X2_TUNE", "").split(",")):      # probes: "key=value,..." kernel-variant knobs (csrc/gemm.hip)
             k, v = kv.split("=")
-            if h.x2_tune(int(k), int(v)) != 0:
-                raise X2HipError("X2_TUNE=%s: %s" % (kv, h.x2_last_error().decode()))
+            set_tune(int(k), int(v), h)
         _lib = h
     return _lib
+
+
+def set_tune(key, value, h=None):
+    """x2_tune(key, value), a process-wide kernel-variant knob; raises when the library refuses (a retired or unknown key, key 2
+    outside -DX2_PROBE builds, a negative key 12) - a refused knob would otherwise measure the default kernel under the variant's name."""
+    h = lib() if h is None else h
+    if h.x2_tune(key, value) != 0:
+        raise X2HipError("x2_tune(%d, %d): %s" % (key, value, h.x2_last_error().decode()))
+
+
+@contextlib.contextmanager
+def tuned(knobs):
+    """Knobs {key: value} set for the body; the PREVIOUS values come back afterwards, in reverse order, also when the body or a later
+    key's set raised.  A key that already holds its value costs no x2_tune call, on entry or on exit."""
+    h = lib()
+    with contextlib.ExitStack() as undo:
+        for key, value in knobs.items():
+            prev = h.x2_tune_get(key)
+            if prev == -1:
+                raise X2HipError("x2_tune_get(%d): no such key" % key)
+            if prev != value:
+                set_tune(key, value, h)
+                undo.callback(set_tune, key, prev, h)
+        yield
 
 
 _get_device = torch._C._cuda_getDevice if hasattr(torch._C, "_cuda_getDevice") else None

@@ -26,12 +26,14 @@ Usage (bench.py; INTEGRATION.md shows the same six lines inside Pretrain.run_ima
         optimizer.step()
 If capture is impossible (e.g. a process group whose collectives cannot be captured: gloo) the object degrades to eager
 execution of `fn` and says so in `.mode`."""
+import contextlib
 import gc
 import os
 
 import torch
 
 from . import kernels as K
+from ._lib import tuned
 
 
 class GraphedStep:
@@ -217,7 +219,7 @@ class SegmentedStep:
         from ._lib import lib as _x2lib
         self._lib = _x2lib() if batch["text_ids"].is_cuda else None
         # (x2_tune(12, ...) is process-wide planning state: it is set around this step's own launches - warm-up, capture, eager runs - and put
-        # back afterwards (_reserve / _unreserve), so that other steps and plain eager calls keep their own tile plans)
+        # back afterwards (_reserved), so that other steps and plain eager calls keep their own tile plans)
         self._queue = None
         # The vision tower as a chain of stages cut at these block numbers (beit2.VisionTransformer.chunk_at): its backward
         # becomes one segment per stage, top first; the weight gradients of every stage but the lowest run as segments of
@@ -292,15 +294,14 @@ class SegmentedStep:
         self.sA.wait_stream(cur)
         side, tie, hook = engine.SIDE.enabled, engine.TIE_WORD_GRAD, engine.GRAD_READY_HOOK
         engine.GRAD_READY_HOOK = None             # an accelerator's early all-reduce hook must not fire from these passes
-        prev_cus = self._reserve()
         try:
-            for _ in range(max(warmup, 1)):       # eager, on the segments' own streams: caches, workspaces, allocator pools
-                self._run("eager")
-            torch.cuda.synchronize()
-            if enabled and os.environ.get("X2_GRAPH", "1") != "0":
-                self._capture(verbose)
+            with self._reserved():
+                for _ in range(max(warmup, 1)):   # eager, on the segments' own streams: caches, workspaces, allocator pools
+                    self._run("eager")
+                torch.cuda.synchronize()
+                if enabled and os.environ.get("X2_GRAPH", "1") != "0":
+                    self._capture(verbose)
         finally:
-            self._unreserve(prev_cus)
             engine.SIDE.enabled, engine.TIE_WORD_GRAD, engine.GRAD_READY_HOOK = side, tie, hook
             # the warm-up / capture passes counted stage calls; an accelerator's GradientBuckets reads the counters of the NEXT
             # eager backward_step (a layer that "ran twice" loses its early all-reduce)
@@ -309,19 +310,9 @@ class SegmentedStep:
             self._agree_across_ranks(verbose)
         cur.wait_stream(self.sA)
 
-    def _reserve(self):
-        """GEMM tile plans of this step's launches leave `reserved_cus` compute units to RCCL's channel kernels (x2_tune key 12);
-        returns the previous value for _unreserve."""
-        if self._lib is None:
-            return None
-        prev = self._lib.x2_tune_get(12)
-        if prev != self.reserved_cus and self._lib.x2_tune(12, self.reserved_cus) != 0:
-            raise RuntimeError("x2_tune(12, %d): %s" % (self.reserved_cus, self._lib.x2_last_error().decode()))
-        return prev
-
-    def _unreserve(self, prev):
-        if self._lib is not None and prev is not None and prev != self.reserved_cus:
-            self._lib.x2_tune(12, prev)
+    def _reserved(self):
+        """GEMM tile plans of the launches inside leave `reserved_cus` compute units to RCCL's channel kernels (x2_tune key 12)."""
+        return tuned({12: self.reserved_cus}) if self._lib is not None else contextlib.nullcontext()
 
     # ------------------------------------------------------------------ set-up
     def _plan_digest(self):
@@ -771,14 +762,13 @@ class SegmentedStep:
             eng = self.engine
             side, tie, hook = eng.SIDE.enabled, eng.TIE_WORD_GRAD, eng.GRAD_READY_HOOK
             eng.GRAD_READY_HOOK = None
-            prev_cus = self._reserve()
             try:
-                self._run("eager")
-                if self.coll and self.reduce_grads and not self.defer_reduce:
-                    with torch.cuda.stream(self.sA):
-                        self._reduce_eager_fallback()
+                with self._reserved():
+                    self._run("eager")
+                    if self.coll and self.reduce_grads and not self.defer_reduce:
+                        with torch.cuda.stream(self.sA):
+                            self._reduce_eager_fallback()
             finally:
-                self._unreserve(prev_cus)
                 eng.SIDE.enabled, eng.TIE_WORD_GRAD, eng.GRAD_READY_HOOK = side, tie, hook
                 eng.STAGE_CALLS.clear()
         cur.wait_stream(self.sA)
