@@ -340,6 +340,27 @@ int x2_vqa_candidates(const long* answer_ids, const long* answer_atts, const int
 int x2_vqa_rerank(const float* loss_rows, int T, const float* vals, const int* ids, int B, int K, float* topk_probs, int* topk_ids, float* scores,
                   void* stream);
 
+/* ---- visual grounding: additive to ABI v14 (csrc/grounding.hip) - XVLMForGrounding (models/model_grounding.py), the box tail of
+ * XVLMBase.get_bbox_loss + box_ops.py (xvlm.py:927-957) and grounding_eval_bbox / computeIoU (dataset/utils.py:363-453).  No existing signature
+ * or struct changes, x2_abi_version() stays 14.  All tensors fp32 (hit: int32), rows of four floats 16-byte aligned (size: 8-byte).
+ *   x2_bbox_loss_fwd : coord[B][4] = sigmoid(logits); per row the L1 sum over the four coordinates and 1 - GIoU of the matched pair, both boxes
+ *       through cx +- w / 2; degenerate flag = some row of either box set has x2 < x1 or y2 < y1 (rows with keep == 0 count): then every row's
+ *       GIoU term is 0 (xvlm.py:943-946, decided on the device).  stat[4] = {sum keep * l1 / num, sum keep * giou / num, flag (0 / 1), num},
+ *       num = sum keep, or B when keep == NULL (num == 0 divides by zero, as the reference does).  One workgroup, fixed summation order, no
+ *       atomics: two runs give the same bits.  1 <= B <= 1048576.
+ *   x2_bbox_loss_bwd : dlogits[B][4] = (g_coord + g_bbox * keep / num * sign(coord - target) + g_giou * keep / num * d(1 - GIoU)/dcoord)
+ *       * coord * (1 - coord); g_bbox / g_giou device scalars (NULL = 0), g_coord [B][4] or NULL; coord and stat are the forward's.  Under the
+ *       flag no GIoU expression is evaluated (no 0 / 0 of an unselected branch).  Ties: sign(0) = 0; max / min of equal edges send the gradient to
+ *       the target's edge (the prediction gets 0); the clamp at exactly 0 passes 0.  1 <= B <= 1048576.
+ *   x2_grounding_iou : per sample, in fp32 and the reference's order: x, w of coord (normalised cxcywh) times size[i][0] (width), y, h times
+ *       size[i][1] (height), centre moved to the corner; then computeIoU against ref_box (pixel xywh): inclusive -1 / +1 pixel edges, strict <
+ *       for "overlaps", union from w * h; hit = iou >= 0.5.  1 <= N <= 16777216.
+ * A B or N outside its range returns -1 and names the entry point in x2_last_error() without launching. */
+int x2_bbox_loss_fwd(const float* logits, const float* target, const float* keep, int B, float* coord, float* stat, void* stream);
+int x2_bbox_loss_bwd(const float* coord, const float* target, const float* keep, const float* stat, const float* g_bbox, const float* g_giou,
+                     const float* g_coord, int B, float* dlogits, void* stream);
+int x2_grounding_iou(const float* coord, const float* ref_box, const float* size, int N, float* iou, int* hit, void* stream);
+
 /* ---- optimizer (csrc/optim.hip) -- "next" row of the scope table ------------------------------------------
  * optim.py:26-104 (transformers==4.12.5 AdamW, eps 1e-8, betas (0.9,0.98), correct_bias) and the global-norm clip of
  * accelerators/apex_ddp_accelerator.py:99-102, as two multi-tensor launches.  table: ntensors records

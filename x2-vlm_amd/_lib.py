@@ -94,6 +94,10 @@ _SIGS = {
     "x2_answer_topk": [P, I, I, I, P, I, I, P, P, P],
     "x2_vqa_candidates": [P, P, P, I, I, I, I, L, P, P, P, P, I, P],
     "x2_vqa_rerank": [P, I, P, P, I, I, P, P, P, P],
+    # visual grounding (additive to ABI v14)
+    "x2_bbox_loss_fwd": [P, P, P, I, P, P, P],
+    "x2_bbox_loss_bwd": [P, P, P, P, P, P, P, I, P, P],
+    "x2_grounding_iou": [P, P, P, I, P, P, P],
 }
 # communicator entry points (csrc/comm.hip): explicit stream / event arguments, bound without the implicit stream of call()
 _COMM_SIGS = {

@@ -955,3 +955,46 @@ def vqa_rerank(loss_rows, vals, ids):
     probs, out_ids, scores = torch.empty_like(vals), torch.empty_like(ids), torch.empty_like(vals)
     call("x2_vqa_rerank", ptr(loss_rows), loss_rows.shape[1], ptr(vals), ptr(ids), B, k, ptr(probs), ptr(out_ids), ptr(scores))
     return probs, out_ids, scores
+
+
+# ----------------------------------------------------------------------------- visual grounding (csrc/grounding.hip)
+
+def _box_rows(t, name):
+    assert t.dtype == F32 and t.dim() == 2 and t.shape[1] == 4 and t.is_contiguous(), "%s: fp32 contiguous [B, 4]" % name
+    return t.shape[0]
+
+
+def bbox_loss_fwd(logits, target, keep=None):
+    """The box tail in one launch: logits / target fp32 [B, 4] (target cxcywh), keep fp32 [B] or None -> (coord fp32 [B, 4] = sigmoid(logits),
+    stat fp32 [4] = {loss_bbox, loss_giou, degenerate flag, num}).  No host round trip: the reference's early-out is the device flag."""
+    B = _box_rows(logits, "logits")
+    assert _box_rows(target, "target") == B
+    assert keep is None or (keep.dtype == F32 and keep.shape == (B,) and keep.is_contiguous())
+    coord = torch.empty_like(logits)
+    stat = torch.empty(4, device=logits.device, dtype=F32)
+    call("x2_bbox_loss_fwd", ptr(logits), ptr(target), ptr(keep), B, ptr(coord), ptr(stat))
+    return coord, stat
+
+
+def bbox_loss_bwd(coord, target, keep, stat, g_bbox=None, g_giou=None, g_coord=None):
+    """dlogits fp32 [B, 4] of bbox_loss_fwd for the device-scalar cotangents g_bbox / g_giou (None = 0) and g_coord fp32 [B, 4] or None."""
+    B = _box_rows(coord, "coord")
+    assert _box_rows(target, "target") == B and stat.dtype == F32 and stat.numel() == 4 and stat.is_contiguous()
+    assert keep is None or (keep.dtype == F32 and keep.shape == (B,) and keep.is_contiguous())
+    for g in (g_bbox, g_giou):
+        assert g is None or (g.dtype == F32 and g.numel() == 1 and g.device == coord.device)
+    assert g_coord is None or _box_rows(g_coord, "g_coord") == B
+    dlogits = torch.empty_like(coord)
+    call("x2_bbox_loss_bwd", ptr(coord), ptr(target), ptr(keep), ptr(stat), ptr(g_bbox), ptr(g_giou), ptr(g_coord), B, ptr(dlogits))
+    return dlogits
+
+
+def grounding_iou(coord, ref_box, size):
+    """grounding_eval_bbox's per-sample arithmetic for a whole set: coord fp32 [N, 4] normalised cxcywh, ref_box fp32 [N, 4] pixel xywh,
+    size fp32 [N, 2] (width, height) -> (iou fp32 [N], hit int32 [N] = iou >= 0.5) under computeIoU's inclusive-pixel convention."""
+    N = _box_rows(coord, "coord")
+    assert _box_rows(ref_box, "ref_box") == N and size.dtype == F32 and size.shape == (N, 2) and size.is_contiguous()
+    iou = torch.empty(N, device=coord.device, dtype=F32)
+    hit = torch.empty(N, device=coord.device, dtype=torch.int32)
+    call("x2_grounding_iou", ptr(coord), ptr(ref_box), ptr(size), N, ptr(iou), ptr(hit))
+    return iou, hit

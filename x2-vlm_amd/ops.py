@@ -88,3 +88,32 @@ class _FrameMean(torch.autograd.Function):
 
 def frame_mean(x, pos, frames):
     return _FrameMean.apply(x, pos, frames)
+
+
+class _BboxLoss(torch.autograd.Function):
+    """sigmoid + L1 + GIoU of matched pairs (xvlm.py:923, 927-957) as kernels.bbox_loss_fwd / _bwd: two launches for the whole box tail.
+    Nothing is read back: the degenerate flag and the box count stay in `stat` on the device, so the function can be captured."""
+
+    @staticmethod
+    def forward(ctx, logits, target, keep):
+        coord, stat = K.bbox_loss_fwd(logits.contiguous(), target, keep)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(coord, target, keep, stat)
+        return coord, stat[0], stat[1]
+
+    @staticmethod
+    def backward(ctx, g_coord, g_bbox, g_giou):
+        coord, target, keep, stat = ctx.saved_tensors
+        if g_coord is None and g_bbox is None and g_giou is None:
+            return None, None, None
+        scalar = lambda g: None if g is None else g.to(torch.float32).reshape(1).contiguous()
+        return K.bbox_loss_bwd(coord, target, keep, stat, scalar(g_bbox), scalar(g_giou),
+                               None if g_coord is None else g_coord.to(torch.float32).contiguous()), None, None
+
+
+def bbox_loss(logits, target, is_image=None):
+    """(output_coord, loss_bbox, loss_giou) of XVLMBase.get_bbox_loss applied to bbox_head's logits [B, 4]: output_coord = sigmoid(logits),
+    the L1 and GIoU means over the rows with is_image == 0 (all rows when None).  Differentiable in logits, through all three outputs."""
+    target = target.detach().to(torch.float32).contiguous()
+    keep = None if is_image is None else (1 - is_image).detach().to(torch.float32).contiguous()
+    return _BboxLoss.apply(logits, target, keep)
