@@ -361,6 +361,30 @@ int x2_bbox_loss_bwd(const float* coord, const float* target, const float* keep,
                      const float* g_coord, int B, float* dlogits, void* stream);
 int x2_grounding_iou(const float* coord, const float* ref_box, const float* size, int N, float* iou, int* hit, void* stream);
 
+/* ---- classification fine-tunes: additive to ABI v14 (csrc/classify.hip) - XVLMForNLVR (models/model_classification.py, NLVR.py): the tail of a
+ * build_mlp head behind its first Linear, LayerNorm -> erf-GELU -> Linear(H -> C) -> F.cross_entropy(ignore_index=-100), and the accuracy of the
+ * evaluation loop.  No existing signature or struct changes, x2_abi_version() stays 14.  All tensors fp32 except labels (int64), pred (int32) and
+ * counts (int64).  1 <= R <= 65536; 4 <= H <= 16384, H % 4 == 0; leading dimensions >= H and % 4 == 0; h, gamma, beta, w, dh 16-byte aligned (rows
+ * are read as float4); 2 <= C <= 16.  No atomics, fixed summation orders: two runs give the same bits.
+ *   x2_cls_tail_fwd : h [R][ldh] (pre-LayerNorm), w [C][H], labels [R] in [0, C) or -100 (any value outside [0, C) is treated as ignored), or
+ *       NULL.  Launch one, a workgroup per row: mean and biased variance in two passes, rstd = 1 / sqrt(var + eps), y = xhat * gamma + beta,
+ *       gelu(y), logits [R][C] = gelu(y) @ w^T + bias, rowstat [R][2] = {mean, rstd}, with labels nll [R] = logsumexp - logit[label] (0 on an
+ *       ignored row).  Launch two (labels only), one workgroup: stat [2] = {sum nll / n_valid, n_valid}; n_valid == 0 gives NaN, as torch does.
+ *       Without labels nll and stat are not touched.
+ *   x2_cls_tail_bwd : dlogits = g_logits + g_loss / n_valid * (softmax(logits) - onehot) on valid rows, g_logits alone on ignored ones; g_loss a
+ *       device scalar (NULL = 0), g_logits [R][C] (NULL = 0); rowstat, logits and stat are the forward's.  Launch one, a workgroup per row:
+ *       dh [R][lddh] through dlogits @ w, gelu'(y) = Phi(y) + y phi(y) and LayerNorm's backward.  Launch two, one thread per column walking rows
+ *       0..R-1 in order: dgamma [H], dbeta [H], dw [C][H] and dbias [C], recomputing xhat, y and gelu(y) from h and rowstat.
+ *   x2_cls_accuracy : one workgroup; pred [R] = the lowest index of the row's maximum (strict >: torch's max(1) tie rule), counts [2] += {rows with
+ *       pred == label, R}: the caller zeroes counts once, launches on one stream accumulate.  NaN logits are outside the contract.
+ * An argument outside its range returns -1 and names the entry point in x2_last_error() without launching. */
+int x2_cls_tail_fwd(const float* h, int ldh, const float* gamma, const float* beta, const float* w, const float* bias, const long* labels, int R,
+                    int H, int C, float eps, float* logits, float* rowstat, float* nll, float* stat, void* stream);
+int x2_cls_tail_bwd(const float* h, int ldh, const float* gamma, const float* beta, const float* w, const float* rowstat, const float* logits,
+                    const long* labels, const float* stat, const float* g_loss, const float* g_logits, int R, int H, int C, float* dh, int lddh,
+                    float* dgamma, float* dbeta, float* dw, float* dbias, void* stream);
+int x2_cls_accuracy(const float* logits, const long* labels, int R, int C, int* pred, long* counts, void* stream);
+
 /* ---- optimizer (csrc/optim.hip) -- "next" row of the scope table ------------------------------------------
  * optim.py:26-104 (transformers==4.12.5 AdamW, eps 1e-8, betas (0.9,0.98), correct_bias) and the global-norm clip of
  * accelerators/apex_ddp_accelerator.py:99-102, as two multi-tensor launches.  table: ntensors records

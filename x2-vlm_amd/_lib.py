@@ -98,6 +98,10 @@ _SIGS = {
     "x2_bbox_loss_fwd": [P, P, P, I, P, P, P],
     "x2_bbox_loss_bwd": [P, P, P, P, P, P, P, I, P, P],
     "x2_grounding_iou": [P, P, P, I, P, P, P],
+    # classification fine-tunes: NLVR2 (additive to ABI v14)
+    "x2_cls_tail_fwd": [P, I, P, P, P, P, P, I, I, I, F, P, P, P, P, P],
+    "x2_cls_tail_bwd": [P, I, P, P, P, P, P, P, P, P, P, I, I, I, P, I, P, P, P, P, P],
+    "x2_cls_accuracy": [P, P, I, I, P, P, P],
 }
 # communicator entry points (csrc/comm.hip): explicit stream / event arguments, bound without the implicit stream of call()
 _COMM_SIGS = {

@@ -998,3 +998,55 @@ def grounding_iou(coord, ref_box, size):
     hit = torch.empty(N, device=coord.device, dtype=torch.int32)
     call("x2_grounding_iou", ptr(coord), ptr(ref_box), ptr(size), N, ptr(iou), ptr(hit))
     return iou, hit
+
+
+# ----------------------------------------------------------------------------- classification fine-tunes (csrc/classify.hip)
+
+def _cls_rows(h, gamma, beta, w, bias):
+    assert h.dtype == F32 and h.dim() == 2 and h.stride(1) == 1 and h.stride(0) >= h.shape[1], "h: fp32 [R, H] rows"
+    R, H = h.shape
+    C = w.shape[0]
+    for t, shape in ((gamma, (H,)), (beta, (H,)), (w, (C, H)), (bias, (C,))):
+        assert t.dtype == F32 and tuple(t.shape) == shape and t.is_contiguous() and t.device == h.device
+    return R, H, C
+
+
+def cls_tail_fwd(h, gamma, beta, w, bias, eps, labels=None):
+    """LayerNorm(eps) -> erf-GELU -> Linear(H -> C) [-> cross_entropy(ignore_index=-100)] of fp32 rows h [R, H] (row stride >= H) in at most two
+    launches -> (logits fp32 [R, C], rowstat fp32 [R, 2] = {mean, rstd}, nll fp32 [R] | None, stat fp32 [2] = {loss, n_valid} | None)."""
+    R, H, C = _cls_rows(h, gamma, beta, w, bias)
+    assert labels is None or (labels.dtype == torch.int64 and labels.shape == (R,) and labels.is_contiguous())
+    logits = torch.empty(R, C, device=h.device, dtype=F32)
+    rowstat = torch.empty(R, 2, device=h.device, dtype=F32)
+    nll = stat = None
+    if labels is not None:
+        nll, stat = torch.empty(R, device=h.device, dtype=F32), torch.empty(2, device=h.device, dtype=F32)
+    call("x2_cls_tail_fwd", ptr(h), h.stride(0), ptr(gamma), ptr(beta), ptr(w), ptr(bias), ptr(labels), R, H, C, eps, ptr(logits), ptr(rowstat),
+         ptr(nll), ptr(stat))
+    return logits, rowstat, nll, stat
+
+
+def cls_tail_bwd(h, gamma, beta, w, rowstat, logits, labels=None, stat=None, g_loss=None, g_logits=None):
+    """(dh [R, H], dgamma [H], dbeta [H], dw [C, H], dbias [C]) of cls_tail_fwd for the device-scalar cotangent g_loss of the loss and g_logits
+    fp32 [R, C] of the logits (None = 0), in two launches."""
+    R, H = h.shape
+    C = w.shape[0]
+    assert rowstat.shape == (R, 2) and logits.shape == (R, C) and rowstat.is_contiguous() and logits.is_contiguous()
+    assert g_loss is None or (g_loss.dtype == F32 and g_loss.numel() == 1 and g_loss.device == h.device and labels is not None and stat is not None)
+    assert g_logits is None or (g_logits.dtype == F32 and g_logits.shape == (R, C) and g_logits.is_contiguous())
+    dh = torch.empty(R, H, device=h.device, dtype=F32)
+    small = torch.empty(2 * H + C * H + C, device=h.device, dtype=F32)
+    dgamma, dbeta, dw, dbias = small[:H], small[H:2 * H], small[2 * H:2 * H + C * H].view(C, H), small[2 * H + C * H:]
+    call("x2_cls_tail_bwd", ptr(h), h.stride(0), ptr(gamma), ptr(beta), ptr(w), ptr(rowstat), ptr(logits), ptr(labels), ptr(stat), ptr(g_loss),
+         ptr(g_logits), R, H, C, ptr(dh), H, ptr(dgamma), ptr(dbeta), ptr(dw), ptr(dbias))
+    return dh, dgamma, dbeta, dw, dbias
+
+
+def cls_accuracy(logits, labels, counts):
+    """pred int32 [R] = the lowest index of each row's maximum; counts int64 [2] += {rows with pred == label, R} (one launch, no read-back)."""
+    R, C = logits.shape
+    assert logits.dtype == F32 and logits.is_contiguous() and labels.dtype == torch.int64 and labels.shape == (R,) and labels.is_contiguous()
+    assert counts.dtype == torch.int64 and counts.shape == (2,) and counts.is_contiguous() and counts.device == logits.device
+    pred = torch.empty(R, device=logits.device, dtype=torch.int32)
+    call("x2_cls_accuracy", ptr(logits), ptr(labels), R, C, ptr(pred), ptr(counts))
+    return pred

@@ -117,3 +117,40 @@ def bbox_loss(logits, target, is_image=None):
     target = target.detach().to(torch.float32).contiguous()
     keep = None if is_image is None else (1 - is_image).detach().to(torch.float32).contiguous()
     return _BboxLoss.apply(logits, target, keep)
+
+
+class _ClsTail(torch.autograd.Function):
+    """LayerNorm -> GELU -> Linear(H -> C) [-> F.cross_entropy(ignore_index=-100)] behind a head's first Linear as kernels.cls_tail_fwd /
+    _bwd: at most two launches each way.  Only h, the logits and the per-row {mean, rstd} are kept for the backward; n_valid stays in `stat` on
+    the device and nothing is read back, so the function can be captured."""
+
+    @staticmethod
+    def forward(ctx, h, gamma, beta, w, bias, eps, labels):
+        if h.stride(-1) != 1 or h.stride(0) % 4 or h.data_ptr() % 16:
+            h = h.contiguous()
+        logits, rowstat, _, stat = K.cls_tail_fwd(h, gamma.detach().contiguous(), beta.detach().contiguous(), w.detach().contiguous(),
+                                                  bias.detach().contiguous(), eps, labels)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(h, gamma, beta, w, rowstat, logits, labels, stat)
+        return logits, (stat[0] if labels is not None else None)
+
+    @staticmethod
+    def backward(ctx, g_logits, g_loss):
+        h, gamma, beta, w, rowstat, logits, labels, stat = ctx.saved_tensors
+        if g_logits is None and g_loss is None:
+            return (None,) * 7
+        g_loss = None if g_loss is None else g_loss.to(torch.float32).reshape(1).contiguous()
+        g_logits = None if g_logits is None else g_logits.to(torch.float32).contiguous()
+        dh, dgamma, dbeta, dw, dbias = K.cls_tail_bwd(h, gamma.detach().contiguous(), beta.detach().contiguous(), w.detach().contiguous(), rowstat,
+                                                      logits, labels, stat, g_loss, g_logits)
+        return dh, dgamma, dbeta, dw, dbias, None, None
+
+
+def cls_tail(seq, h, targets=None):
+    """(logits [R, C], loss | None) of a build_mlp head's tail seq[1] (LayerNorm), seq[2] (GELU), seq[3] (Linear) on the rows h = seq[0](x), the
+    loss being F.cross_entropy(logits, targets, ignore_index=-100) when targets are given.  Differentiable through both outputs."""
+    if not isinstance(h, torch.Tensor) or not h.is_cuda:
+        from .model_generation import _HOST_PATH
+        raise NotImplementedError(_HOST_PATH % "ops.cls_tail")
+    labels = None if targets is None else targets.detach().to(torch.int64).contiguous()
+    return _ClsTail.apply(h, seq[1].weight, seq[1].bias, seq[3].weight, seq[3].bias, seq[1].eps, labels)
