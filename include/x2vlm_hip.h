@@ -385,6 +385,50 @@ int x2_cls_tail_bwd(const float* h, int ldh, const float* gamma, const float* be
                     float* dgamma, float* dbeta, float* dw, float* dbias, void* stream);
 int x2_cls_accuracy(const float* logits, const long* labels, int R, int C, int* pred, long* counts, void* stream);
 
+/* ---- wide-label classification head: additive to ABI v14 (csrc/classify_wide.hip) - XVLMForClassification and XVLMForVQAClassification
+ * (models/model_classification.py): the row work around the logits GEMM of a build_mlp head with more than 16 labels.  The logits themselves are
+ * x2_gemm_nt(act, Wp, bias_p) -> fp32 [R][Cp], Cp = C rounded up to 64 with zero weight rows and zero bias: the pad columns hold 0, and every
+ * entry point here reads columns [0, C) only.  No existing signature changes, x2_abi_version() stays 14.  fp32 tensors except act and dl (bf16,
+ * round to nearest even), offs (int32), targets / labels / counts (int64), pred / hit (int32).  1 <= R <= 65536; 4 <= H <= 16384, H % 4 == 0;
+ * 2 <= C <= 2^20; ldh, lda, ldd, lddh >= H and % 4 == 0 with h, gamma, beta, dact, dh 16-byte and act 8-byte aligned; ldl, ldt, ldg >= C (any value:
+ * rows are read as float4 when the base is 16-byte aligned and the leading dimension % 4 == 0, as scalars otherwise, with the same arithmetic);
+ * Cp >= C, Cp % 4 == 0, lddl >= Cp and % 4 == 0, dl 8-byte aligned.  No atomics; summation orders are fixed (file header): two runs give the same
+ * bits.
+ *   x2_lngelu_fwd : one launch, a workgroup per row.  mean, biased variance as the mean of (x - mean)^2 in a second pass, rstd = 1 / sqrt(var + eps),
+ *       act [R][lda] = bf16(erf-GELU(xhat * gamma + beta)), rowstat [R][2] = {mean, rstd}.  Columns [H, lda) of act are not written.
+ *   x2_lngelu_bwd : launch one, a workgroup per row: dy = dact * gelu'(y), LayerNorm's backward -> dh [R][lddh].  Launch two, one thread per column
+ *       walking rows 0..R-1 in order: dgamma [H], dbeta [H].  xhat and y are recomputed from h and rowstat.
+ *   x2_soft_ce_fwd : row r owns the entries offs[r] .. offs[r+1]-1 of targets [T] and weights [T] (NULL = 1); offs [R+1] is required.  Launch one, a
+ *       workgroup per row: lse [R] over columns [0, C) (max, then sum of exp(z - max)), rowloss [R] = sum_j w_j (lse - z[t_j]) in index order; an
+ *       entry with t_j outside [0, C) (ignore_index's -100) is skipped, a row without entries gives 0.  Launch two, one workgroup: stat [2] =
+ *       {sum_r rowloss / denom, denom}; denom_mode 0: denom = R (the loss.sum() / image.size(0) of XVLMForVQAClassification), 1: the number of
+ *       non-skipped entries (with offs = 0..R and NULL weights F.cross_entropy(ignore_index=-100); no such entry gives 0 / 0 = NaN, as torch does).
+ *       targets == NULL: no loss is asked for, only lse is written and rowloss / stat are not touched.
+ *   x2_kl_ce_fwd : lse, lse_t [R] of the logits and the teacher [R][ldt], rowloss [R] = sum_c p_c ((t_c - lse_t) - (z_c - lse)) with
+ *       p_c = exp(t_c - lse_t) (p_c == 0 contributes 0), stat = {sum_r rowloss / R, R}: nn.KLDivLoss('none')(log_softmax(z), softmax(t)).sum() / R.
+ *   x2_soft_ce_bwd : one launch, a workgroup per row: dl [R][lddl] = bf16(g_logits[r][c] + g_loss / denom * (Wr softmax(z)[c] - sum_{j: t_j = c} w_j))
+ *       for c < C and 0 for C <= c < Cp; Wr = the sum of the row's non-skipped weights, denom = the forward's stat[1]; duplicates of a column add in
+ *       index order (the entries are staged in LDS 256 at a time: no maximum k).  g_loss: device scalar; g_logits [R][ldg]; either may be NULL
+ *       (= 0); with g_loss NULL the loss's tensors are not read and may be NULL.
+ *   x2_kl_ce_bwd : the same for the KL loss: dl = bf16(g_logits + g_loss / R * (softmax(z) - p)).
+ *   x2_cls_accuracy_rows : launch one, a workgroup per row: pred [R] = the lowest index of the maximum over columns [0, C) (prediction.max(1)'s
+ *       tie rule), hit [R] = (pred == label); a label of -100 is a miss.  Launch two, one workgroup: counts [2] += {sum hit, R} by a plain
+ *       read-modify-write (the caller zeroes counts once; launches on one stream accumulate).  NaN logits are outside the contract.
+ * An argument outside its range returns -1 and names the entry point in x2_last_error() without launching. */
+int x2_lngelu_fwd(const float* h, int ldh, const float* gamma, const float* beta, int R, int H, float eps, void* act, int lda, float* rowstat,
+                  void* stream);
+int x2_lngelu_bwd(const float* dact, int ldd, const float* h, int ldh, const float* gamma, const float* beta, const float* rowstat, int R, int H,
+                  float* dh, int lddh, float* dgamma, float* dbeta, void* stream);
+int x2_soft_ce_fwd(const float* logits, int ldl, int R, int C, const int* offs, const long* targets, const float* weights, int denom_mode, float* lse,
+                   float* rowloss, float* stat, void* stream);
+int x2_kl_ce_fwd(const float* logits, int ldl, const float* teacher, int ldt, int R, int C, float* lse, float* lse_t, float* rowloss, float* stat,
+                 void* stream);
+int x2_soft_ce_bwd(const float* logits, int ldl, int R, int C, const int* offs, const long* targets, const float* weights, const float* lse,
+                   const float* stat, const float* g_loss, const float* g_logits, int ldg, void* dl, int lddl, int Cp, void* stream);
+int x2_kl_ce_bwd(const float* logits, int ldl, const float* teacher, int ldt, int R, int C, const float* lse, const float* lse_t, const float* g_loss,
+                 const float* g_logits, int ldg, void* dl, int lddl, int Cp, void* stream);
+int x2_cls_accuracy_rows(const float* logits, int ldl, const long* labels, int R, int C, int* pred, int* hit, long* counts, void* stream);
+
 /* ---- optimizer (csrc/optim.hip) -- "next" row of the scope table ------------------------------------------
  * optim.py:26-104 (transformers==4.12.5 AdamW, eps 1e-8, betas (0.9,0.98), correct_bias) and the global-norm clip of
  * accelerators/apex_ddp_accelerator.py:99-102, as two multi-tensor launches.  table: ntensors records

@@ -1,0 +1,166 @@
+#!/usr/bin/env python3
+"""VQA classification fine-tune train step (XVLMForVQAClassification forward + backward, train mode) and its head alone.  Geometry: BEiT2-large
+384 px (N = 577), BERT-large 12 + 6 layers, C = 3129 answers, 40 tokens, the per-GPU batch of configs/finetune/vqa2_large.yaml (2; that file
+trains at 768 px), three answers per question, synthetic weights.  Prints one JSON line with
+  eager / graphed   ms per step (median of HIP-event intervals, with min and max), launched eagerly and as one graph.GraphedStep replay
+  head              ms per forward + backward of the head alone - Linear(H/2 -> H) -> LayerNorm -> GELU -> Linear(H -> 3129) -> the k-expanded
+                    weighted cross-entropy on fp32 rows [R, H/2] - at [64, 1536 -> 3129] (X2VLM-base at batch 64) and [32, 2048 -> 3129]
+                    (X2VLM-large at batch 32): the first Linear + ops.cls_wide, as the model runs them, against what the parent commit offers,
+                    ops.mlp_head (whose last layer is the fp32 ops.linear) followed by ATen repeat_interleave and
+                    F.cross_entropy(reduction='none') times the weights.  The two forms alternate in four rounds; eager launches, so host
+                    time is part of what is compared
+Nothing is asserted on the times.  The optimizer step is not timed.
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HEAD_SHAPES = [(64, 1536), (32, 2048)]
+LABELS = 3129
+ANSWERS = 3
+ROUNDS = 4
+
+
+def write_configs(d):
+    vis = os.path.join(d, "config_beit2_large.json")
+    with open(vis, "w") as f:
+        json.dump({"ckpt": "", "vision_width": 1024, "patch_size": 16}, f)
+    tdir = os.path.join(d, "bert-large-uncased-12l")
+    os.makedirs(tdir, exist_ok=True)
+    with open(os.path.join(tdir, "config.json"), "w") as f:
+        json.dump(dict(vocab_size=30522, hidden_size=1024, num_attention_heads=16, intermediate_size=4096, max_position_embeddings=512,
+                       type_vocab_size=2, hidden_act="gelu", hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1, layer_norm_eps=1e-12,
+                       initializer_range=0.02, pad_token_id=0, model_type="bert"), f)
+    return dict(use_beit_v2=True, vision_config=vis, image_res=384, patch_size=16, vision_num_hidden_layers=24, text_encoder=tdir,
+                text_num_hidden_layers=18, text_fusion_start_at=12, embed_dim=256, temp=0.07, max_tokens=40, num_labels=LABELS)
+
+
+def intervals(torch, fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
+    ev[0].record()
+    for i in range(steps):
+        fn()
+        ev[i + 1].record()
+    torch.cuda.synchronize()
+    return [ev[i].elapsed_time(ev[i + 1]) for i in range(steps)]
+
+
+def summary(ms):
+    ms = sorted(ms)
+    return ms[len(ms) // 2], ms[0], ms[-1]
+
+
+def answers(torch, dev, R):
+    """ANSWERS weighted targets per row: (k list, k device tensor, offs, targets, weights)"""
+    g = torch.Generator().manual_seed(5)
+    k = [ANSWERS] * R
+    targets = torch.randint(0, LABELS, (ANSWERS * R,), generator=g).to(dev)
+    weights = (torch.randint(1, 11, (ANSWERS * R,), generator=g).float() / 10.0).to(dev)
+    offs = (torch.arange(R + 1, dtype=torch.int32) * ANSWERS).to(dev)
+    return k, torch.tensor(k, device=dev), offs, targets, weights
+
+
+def bench_head(torch, ops, xvlm, first_linear, dev, R, H, steps):
+    """forward + backward of the head on the same rows through both forms -> {name: (median, min, max)}, {name: loss}"""
+    import torch.nn.functional as F
+    head = xvlm.build_mlp(H // 2, LABELS).to(dev)                 # Linear(H/2 -> H), LayerNorm(H), GELU, Linear(H -> 3129)
+    x = torch.randn(R, H // 2, device=dev, requires_grad=True)
+    _, k_dev, offs, targets, weights = answers(torch, dev, R)
+    weights_of_head = list(head.parameters())
+    seen = {}
+
+    def clear():
+        x.grad = None
+        for p in weights_of_head:
+            p.grad = None
+
+    def parent():
+        clear()
+        prediction = ops.mlp_head(head, x)
+        loss = (weights * F.cross_entropy(torch.repeat_interleave(prediction, k_dev, dim=0, output_size=targets.shape[0]), targets,
+                                          ignore_index=-100, reduction="none")).sum() / R
+        loss.backward()
+        seen["parent"] = loss.detach()
+
+    def wide():
+        clear()
+        _, loss = ops.cls_wide(head, first_linear(head, x), targets=targets, offs=offs, weights=weights, denom_mode=0)
+        loss.backward()
+        seen["cls_wide"] = loss.detach()
+
+    forms = [("parent", parent), ("cls_wide", wide)]
+    ms = {name: [] for name, _ in forms}
+    for _ in range(ROUNDS):                                       # the forms alternate, so that a busy host meets both
+        for name, fn in forms:
+            ms[name] += intervals(torch, fn, steps // ROUNDS, 10)
+    return {k: summary(v) for k, v in ms.items()}, {k: round(float(v), 6) for k, v in seen.items()}
+
+
+def bench(args):
+    import torch
+    mcl = importlib.import_module("x2-vlm_amd.model_classification")
+    graph = importlib.import_module("x2-vlm_amd.graph")
+    ops = importlib.import_module("x2-vlm_amd.ops")
+    xvlm = importlib.import_module("x2-vlm_amd.xvlm")
+    synthetic = importlib.import_module("x2-vlm_amd.synthetic")
+    dev = torch.device("cuda:0")
+    out = {}
+    for R, H in HEAD_SHAPES:
+        t, losses = bench_head(torch, ops, xvlm, mcl._head_first_linear, dev, R, H, args.head_steps)
+        for name, (med, lo, hi) in t.items():
+            out["head_%s_ms_%dx%d" % (name, R, H)] = round(med, 4)
+            out["head_%s_ms_min_max_%dx%d" % (name, R, H)] = [round(lo, 4), round(hi, 4)]
+        out["head_loss_%dx%d" % (R, H)] = losses
+    if args.head_only:
+        print(json.dumps(dict({"probe": "vqa classification head (fwd+bwd)", "head_steps": args.head_steps}, **out)))
+        return
+    with tempfile.TemporaryDirectory() as d:
+        model = mcl.XVLMForVQAClassification(write_configs(d))
+    synthetic.synth_state_dict(model, 0)
+    model = model.to(dev).train()
+    B = args.batch
+    b = synthetic.synth_batch(1, B, 40, 384, 30522, ragged=True)
+    image, ids, atts = b["image"].to(dev), b["text_ids"].to(dev), b["text_atts"].to(dev)
+    _, k_dev, _, targets, weights = answers(torch, dev, B)
+    params = list(model.parameters())
+
+    def step():
+        for p in params:
+            p.grad = None
+        loss = model(image, ids, atts, targets=targets, k=k_dev, weights=weights, train=True)
+        loss.backward()
+        return loss
+
+    med, lo, hi = summary(intervals(torch, step, args.steps, args.warmup))
+    out.update(eager_ms_per_step=round(med, 2), eager_ms_min_max=[round(lo, 2), round(hi, 2)])
+    gstep = graph.GraphedStep(step)
+    out["graph_mode"] = gstep.mode
+    med, lo, hi = summary(intervals(torch, gstep, args.steps, args.warmup))
+    out.update(graphed_ms_per_step=round(med, 2), graphed_ms_min_max=[round(lo, 2), round(hi, 2)], questions_per_s=round(B * 1000.0 / med, 1))
+    loss = gstep()
+    print(json.dumps(dict({"probe": "vqa classification train step (fwd+bwd)", "geometry": "BEiT2-large 384px + BERT-large 12+6 layers, C = %d, "
+                           "batch %d, %d answers per question, 40 tokens, train mode" % (LABELS, B, ANSWERS), "steps": args.steps,
+                           "warmup": args.warmup, "loss": round(float(loss), 5)}, **out)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--head-steps", type=int, default=200)
+    ap.add_argument("--head-only", action="store_true")
+    bench(ap.parse_args())
+
+
+if __name__ == "__main__":
+    main()

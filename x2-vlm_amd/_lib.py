@@ -102,6 +102,14 @@ _SIGS = {
     "x2_cls_tail_fwd": [P, I, P, P, P, P, P, I, I, I, F, P, P, P, P, P],
     "x2_cls_tail_bwd": [P, I, P, P, P, P, P, P, P, P, P, I, I, I, P, I, P, P, P, P, P],
     "x2_cls_accuracy": [P, P, I, I, P, P, P],
+    # wide-label classification head: XVLMForClassification, XVLMForVQAClassification (additive to ABI v14)
+    "x2_lngelu_fwd": [P, I, P, P, I, I, F, P, I, P, P],
+    "x2_lngelu_bwd": [P, I, P, I, P, P, P, I, I, P, I, P, P, P],
+    "x2_soft_ce_fwd": [P, I, I, I, P, P, P, I, P, P, P, P],
+    "x2_kl_ce_fwd": [P, I, P, I, I, I, P, P, P, P, P],
+    "x2_soft_ce_bwd": [P, I, I, I, P, P, P, P, P, P, P, I, P, I, I, P],
+    "x2_kl_ce_bwd": [P, I, P, I, I, I, P, P, P, P, I, P, I, I, P],
+    "x2_cls_accuracy_rows": [P, I, P, I, I, P, P, P, P],
 }
 # communicator entry points (csrc/comm.hip): explicit stream / event arguments, bound without the implicit stream of call()
 _COMM_SIGS = {

@@ -1050,3 +1050,125 @@ def cls_accuracy(logits, labels, counts):
     pred = torch.empty(R, device=logits.device, dtype=torch.int32)
     call("x2_cls_accuracy", ptr(logits), ptr(labels), R, C, ptr(pred), ptr(counts))
     return pred
+
+
+# ----------------------------------------------------------------------------- wide-label classification head (csrc/classify_wide.hip)
+
+def _f32_rows(t, cols, name):
+    assert t.dtype == F32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[1] >= cols and t.stride(0) >= cols, "%s: fp32 rows of >= %d columns" % (name, cols)
+    return t.stride(0)
+
+
+def lngelu_fwd(h, gamma, beta, eps, act=None):
+    """LayerNorm(eps) -> erf-GELU of fp32 rows h [R, H] (row stride >= H) in one launch -> (act bf16 [R, H], the logits GEMM's operand,
+    rowstat fp32 [R, 2] = {mean, rstd})."""
+    R, H = h.shape
+    _f32_rows(h, H, "h")
+    for t in (gamma, beta):
+        assert t.dtype == F32 and tuple(t.shape) == (H,) and t.is_contiguous() and t.device == h.device
+    if act is None:
+        act = torch.empty(R, H, device=h.device, dtype=BF16)
+    assert act.dtype == BF16 and act.shape == (R, H)
+    rowstat = torch.empty(R, 2, device=h.device, dtype=F32)
+    call("x2_lngelu_fwd", ptr(h), h.stride(0), ptr(gamma), ptr(beta), R, H, eps, ptr(act), _rows(act), ptr(rowstat))
+    return act, rowstat
+
+
+def lngelu_bwd(dact, h, gamma, beta, rowstat):
+    """(dh [R, H], dgamma [H], dbeta [H]) of lngelu_fwd for the fp32 cotangent dact [R, H] of the (unrounded) activation, in two launches."""
+    R, H = h.shape
+    _f32_rows(h, H, "h"), _f32_rows(dact, H, "dact")
+    assert dact.shape == (R, H) and rowstat.shape == (R, 2) and rowstat.is_contiguous()
+    dh = torch.empty(R, H, device=h.device, dtype=F32)
+    small = torch.empty(2 * H, device=h.device, dtype=F32)
+    call("x2_lngelu_bwd", ptr(dact), dact.stride(0), ptr(h), h.stride(0), ptr(gamma), ptr(beta), ptr(rowstat), R, H, ptr(dh), H, ptr(small),
+         ptr(small[H:]))
+    return dh, small[:H], small[H:]
+
+
+def _entries(R, offs, targets, weights, dev):
+    """checked (targets, weights); an empty batch of entries (T = 0, every offs 0) gets one never-read element: a NULL targets pointer means
+    'no loss asked for' to the library"""
+    assert offs.dtype == torch.int32 and offs.shape == (R + 1,) and offs.is_contiguous() and offs.device == dev
+    assert targets.dtype == torch.int64 and targets.dim() == 1 and targets.is_contiguous() and targets.device == dev
+    assert weights is None or (weights.dtype == F32 and weights.shape == targets.shape and weights.is_contiguous() and weights.device == dev)
+    if targets.numel() == 0:
+        targets = targets.new_full((1,), -100)
+        weights = None if weights is None else weights.new_zeros(1)
+    return targets, weights
+
+
+def soft_ce_fwd(logits, C, offs, targets=None, weights=None, denom_mode=0):
+    """Cross-entropy with several weighted targets per row over columns [0, C) of fp32 logits [R, >= C]: row r owns entries offs[r] .. offs[r+1]-1
+    -> (lse [R], rowloss [R] | None, stat [2] = {sum rowloss / denom, denom} | None); denom = R (mode 0) or the non-skipped entries (mode 1).
+    Without targets only lse is computed."""
+    R = logits.shape[0]
+    ldl = _f32_rows(logits, C, "logits")
+    dev = logits.device
+    lse = torch.empty(R, device=dev, dtype=F32)
+    rowloss = stat = None
+    if targets is not None:
+        targets, weights = _entries(R, offs, targets, weights, dev)
+        rowloss, stat = torch.empty(R, device=dev, dtype=F32), torch.empty(2, device=dev, dtype=F32)
+    call("x2_soft_ce_fwd", ptr(logits), ldl, R, C, ptr(offs), ptr(targets), ptr(weights), denom_mode, ptr(lse), ptr(rowloss), ptr(stat))
+    return lse, rowloss, stat
+
+
+def kl_ce_fwd(logits, teacher, C):
+    """KLDivLoss('none')(log_softmax(logits), softmax(teacher)).sum() / R over columns [0, C) -> (lse [R], lse_t [R], rowloss [R], stat [2])."""
+    R = logits.shape[0]
+    ldl, ldt = _f32_rows(logits, C, "logits"), _f32_rows(teacher, C, "teacher")
+    assert teacher.shape[0] == R and teacher.device == logits.device
+    buf = torch.empty(3 * R + 2, device=logits.device, dtype=F32)
+    lse, lse_t, rowloss, stat = buf[:R], buf[R:2 * R], buf[2 * R:3 * R], buf[3 * R:]
+    call("x2_kl_ce_fwd", ptr(logits), ldl, ptr(teacher), ldt, R, C, ptr(lse), ptr(lse_t), ptr(rowloss), ptr(stat))
+    return lse, lse_t, rowloss, stat
+
+
+def _dl_out(R, C, Cp, g_logits, dev, dl):
+    Cp = round_up(C, 64) if Cp is None else Cp
+    if dl is None:
+        dl = torch.empty(R, Cp, device=dev, dtype=BF16)
+    assert dl.dtype == BF16 and dl.shape == (R, Cp) and dl.stride(1) == 1
+    ldg = 0 if g_logits is None else _f32_rows(g_logits, C, "g_logits")
+    return dl, Cp, ldg
+
+
+def soft_ce_bwd(R, C, *, logits=None, offs=None, targets=None, weights=None, lse=None, stat=None, g_loss=None, g_logits=None, Cp=None, dl=None):
+    """dlogits bf16 [R, Cp] (pad columns zero) of soft_ce_fwd: g_logits + g_loss / denom * (Wr softmax - sum of the row's weights per column);
+    g_loss a device scalar, g_logits fp32 [R, >= C]; either may be None (= 0).  One launch."""
+    dev = (logits if logits is not None else g_logits).device
+    dl, Cp, ldg = _dl_out(R, C, Cp, g_logits, dev, dl)
+    ldl = 0
+    if g_loss is not None:
+        ldl = _f32_rows(logits, C, "logits")
+        targets, weights = _entries(R, offs, targets, weights, dev)
+        assert g_loss.dtype == F32 and g_loss.numel() == 1 and g_loss.device == dev and lse.shape == (R,) and stat.shape == (2,)
+    call("x2_soft_ce_bwd", ptr(logits), ldl, R, C, ptr(offs), ptr(targets), ptr(weights), ptr(lse), ptr(stat), ptr(g_loss), ptr(g_logits), ldg,
+         ptr(dl), _rows(dl), Cp)
+    return dl
+
+
+def kl_ce_bwd(R, C, *, logits=None, teacher=None, lse=None, lse_t=None, g_loss=None, g_logits=None, Cp=None, dl=None):
+    """dlogits bf16 [R, Cp] (pad columns zero) of kl_ce_fwd: g_logits + g_loss / R * (softmax(logits) - softmax(teacher)).  One launch."""
+    dev = (logits if logits is not None else g_logits).device
+    dl, Cp, ldg = _dl_out(R, C, Cp, g_logits, dev, dl)
+    ldl = ldt = 0
+    if g_loss is not None:
+        ldl, ldt = _f32_rows(logits, C, "logits"), _f32_rows(teacher, C, "teacher")
+        assert g_loss.dtype == F32 and g_loss.numel() == 1 and g_loss.device == dev and lse.shape == (R,) and lse_t.shape == (R,)
+    call("x2_kl_ce_bwd", ptr(logits), ldl, ptr(teacher), ldt, R, C, ptr(lse), ptr(lse_t), ptr(g_loss), ptr(g_logits), ldg, ptr(dl), _rows(dl), Cp)
+    return dl
+
+
+def cls_accuracy_rows(logits, labels, counts, C=None):
+    """pred int32 [R] = the lowest index of each row's maximum over columns [0, C); hit int32 [R] = (pred == label); counts int64 [2] +=
+    {sum hit, R} (two launches, no read-back) -> (pred, hit)."""
+    R = logits.shape[0]
+    C = logits.shape[1] if C is None else C
+    ldl = _f32_rows(logits, C, "logits")
+    assert labels.dtype == torch.int64 and labels.shape == (R,) and labels.is_contiguous()
+    assert counts.dtype == torch.int64 and counts.shape == (2,) and counts.is_contiguous() and counts.device == logits.device
+    out = torch.empty(2, R, device=logits.device, dtype=torch.int32)
+    call("x2_cls_accuracy_rows", ptr(logits), ldl, ptr(labels), R, C, ptr(out[0]), ptr(out[1]), ptr(counts))
+    return out[0], out[1]

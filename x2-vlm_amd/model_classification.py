@@ -1,4 +1,5 @@
-"""NLVR2 fine-tune and evaluation on the MI355X stages (models/model_classification.py: XVLMForNLVR; NLVR.py).
+"""Classification fine-tunes and their evaluation on the MI355X stages (models/model_classification.py: XVLMForNLVR, XVLMForClassification,
+XVLMForVQAClassification; NLVR.py, VQA_msrvtt.py, VQA_msvd.py).
 
   XVLMForNLVR    forward(image, text_ids, text_atts, targets, train=True): image holds image0 stacked over image1 ([2B, ...], as NLVR.py builds
                  it).  One vision pass over the 2B images, one fusion pass over 2B text rows, the fusion CLS rows b and B + b side by side as
@@ -12,6 +13,15 @@ The text rows.  The reference calls get_cross_embeds(text_ids=...) once per imag
   otherwise:     the two calls repeat the text-only layers on identical inputs, so they run once on B rows (get_text_embeds) and the 2B fusion rows
                  read them through _fusion_cls with t_idx = [0..B, 0..B] and kv = [0..2B): row r attends to image r.
 Per row both routes are the reference's arithmetic.  Tokenizer, data loader and the NLVR.py script stay with the caller.
+
+  XVLMForClassification      forward(image, text_ids, text_atts, targets=None, train=True): the CLS row of the 12-layer text pass (image is None), of
+                             the vision pass (text_ids is None; 5-D video batches go through the frame mean) or of the fusion pass, then cls_head.
+                             Up to 16 labels the tail is ops.cls_tail, above that ops.cls_wide with one target per row and the mean over the
+                             non-ignored rows (F.cross_entropy(ignore_index=-100)).  num_labels == 1 (the MSE regression) is not built.
+  XVLMForVQAClassification   forward(image, text_ids, text_atts, targets=None, k=None, weights=None, train=True, answer_pred=None,
+                             return_logits=False): row b owns k[b] of the T targets and weights, loss = sum_b sum_j w_j CE(prediction[b], t_j) / B
+                             without the reference's repeat of the prediction rows; with answer_pred the KL divergence to softmax(answer_pred).
+  ClassificationAccuracy     NLVRAccuracy for any number of labels (kernels.cls_accuracy_rows: a workgroup per row).
 """
 import torch
 
@@ -60,6 +70,97 @@ class XVLMForNLVR(XVLMBase):
         return loss if train else prediction
 
 
+def _head_first_linear(head, x):
+    """cls_head[0] as XVLMForNLVR.forward runs it: ops.mlp_head's rule for its first Linear"""
+    w0 = head[0].weight
+    if w0.shape[1] % 64 == 0 and w0.shape[0] % 8 == 0 and x.numel() % 4 == 0:
+        return ops.LinearBf16Fn.apply(x, w0, head[0].bias)
+    return ops.linear(x, w0, head[0].bias)
+
+
+class XVLMForClassification(XVLMBase):
+    """VQA_msrvtt.py / VQA_msvd.py (video QA as 1500- / 1000-way classification) and the single-tower classifiers."""
+
+    def __init__(self, config):
+        super().__init__(config, load_vision_params=False, load_text_params=False, use_contrastive_loss=False, use_matching_loss=False,
+                         use_mlm_loss=False, use_bbox_loss=False)
+        feature_dim = self.vision_width if config.get("task_name") == "imagenet" else self.text_width
+        self.num_labels = config["num_labels"]
+        self.cls_head = build_mlp(input_dim=feature_dim, output_dim=self.num_labels)
+
+    def forward(self, image, text_ids, text_atts, targets=None, train=True):
+        probe = text_ids if image is None else image
+        if not isinstance(probe, torch.Tensor) or not probe.is_cuda:
+            raise NotImplementedError(_HOST_PATH % "XVLMForClassification.forward")
+        if self.num_labels == 1:
+            raise NotImplementedError("XVLMForClassification: the MSE regression head (num_labels == 1) is not built on the HIP path")
+        if image is None:
+            output_cls = self.get_text_embeds_12L(text_ids, text_atts)[:, 0, :]
+        elif text_ids is None:
+            image_embeds, _ = self.get_vision_embeds(image)
+            output_cls = image_embeds[:, 0, :]
+        else:
+            image_embeds, image_atts = self.get_vision_embeds(image)
+            output_cls = self.get_cross_embeds(image_embeds, image_atts, text_ids=text_ids, text_atts=text_atts)[:, 0, :]
+        h = _head_first_linear(self.cls_head, output_cls)
+        if self.num_labels <= 16:
+            prediction, loss = ops.cls_tail(self.cls_head, h, targets if train else None)
+        elif train:
+            offs = torch.arange(h.shape[0] + 1, device=h.device, dtype=torch.int32)          # one target per row
+            prediction, loss = ops.cls_wide(self.cls_head, h, targets=targets, offs=offs, denom_mode=1)
+        else:
+            prediction, loss = ops.cls_wide(self.cls_head, h)
+        return loss if train else prediction
+
+
+class XVLMForVQAClassification(XVLMBase):
+    """VQA v2 over a closed answer set (3129 labels by convention): k-expanded weighted cross-entropy, KL distillation, return_logits."""
+
+    def __init__(self, config):
+        super().__init__(config, load_vision_params=False, load_text_params=False, use_contrastive_loss=False, use_matching_loss=False,
+                         use_mlm_loss=False, use_bbox_loss=False)
+        self.num_labels = config["num_labels"]
+        self.cls_head = build_mlp(input_dim=self.text_width, output_dim=self.num_labels)
+        self.init_params = ["cls_head." + n for n, _ in self.cls_head.named_parameters()]
+
+    @staticmethod
+    def _offsets(k, B, T, device):
+        """int32 [B + 1]: the exclusive prefix sum of k.  A device tensor stays on the device (no synchronisation: the caller guarantees
+        sum(k) <= T); a list or a host tensor is checked here."""
+        if isinstance(k, torch.Tensor) and k.is_cuda:
+            assert k.numel() == B, "k must hold one count per row"
+            offs = torch.zeros(B + 1, device=device, dtype=torch.int32)
+            offs[1:] = torch.cumsum(k.reshape(-1), 0)
+            return offs
+        ks = [int(n) for n in (k.tolist() if isinstance(k, torch.Tensor) else k)]
+        if len(ks) != B or min(ks) < 0 or sum(ks) != T:
+            raise ValueError("k must hold %d non-negative counts that sum to the %d targets (got %s)" % (B, T, ks))
+        offs = [0]
+        for n in ks:
+            offs.append(offs[-1] + n)
+        return torch.tensor(offs, dtype=torch.int32).to(device)
+
+    def forward(self, image, text_ids, text_atts, targets=None, k=None, weights=None, train=True, answer_pred=None, return_logits=False):
+        if not isinstance(image, torch.Tensor) or not image.is_cuda:
+            raise NotImplementedError(_HOST_PATH % "XVLMForVQAClassification.forward")
+        if self.num_labels <= 16:
+            raise ValueError("XVLMForVQAClassification: num_labels=%d; the wide head serves more than 16 labels" % self.num_labels)
+        image_embeds, image_atts = self.get_vision_embeds(image)
+        output_cls = self.get_cross_embeds(image_embeds, image_atts, text_ids=text_ids, text_atts=text_atts)[:, 0, :]
+        h = _head_first_linear(self.cls_head, output_cls)
+        if not train:
+            return ops.cls_wide(self.cls_head, h)[0]
+        if answer_pred is not None:
+            return ops.cls_wide(self.cls_head, h, teacher=answer_pred)[1]
+        B = h.shape[0]
+        assert image.size(0) == B
+        targets = targets.to(h.device).view(-1)
+        weights = torch.as_tensor(weights, dtype=torch.float32).to(h.device).view(-1)
+        prediction, loss = ops.cls_wide(self.cls_head, h, targets=targets, offs=self._offsets(k, B, targets.shape[0], h.device), weights=weights,
+                                        denom_mode=0)
+        return (loss, prediction) if return_logits else loss
+
+
 class NLVRAccuracy:
     """NLVR.py:88-96 without the per-batch host round trip: update() is one launch (kernels.cls_accuracy: the row argmax under max(1)'s tie rule,
     then counts += {correct, rows} on the device), result() reads the two counters back once.  correct / counted equals the reference's
@@ -87,3 +188,21 @@ class NLVRAccuracy:
     def formatted(self):
         """the dict NLVR.py:96 returns: every value as '{:.4f}'"""
         return {k: "{:.4f}".format(v) for k, v in self.result().items()}
+
+
+class ClassificationAccuracy(NLVRAccuracy):
+    """NLVRAccuracy for any number of labels (VQA_msrvtt.py:88-96): update() is kernels.cls_accuracy_rows - a workgroup per row takes the lowest
+    index of the row's maximum, a second launch adds {correct, rows} to the device counters; a target of -100 counts as a miss, as
+    (targets == pred_class).sum() / targets.size(0) does.  result() / formatted() are NLVRAccuracy's."""
+
+    def update(self, prediction, targets):
+        """prediction fp32 [B, C] (a HIP tensor; a column view of wider rows is read in place), targets [B] -> pred_class int32 [B]"""
+        if not isinstance(prediction, torch.Tensor) or not prediction.is_cuda:
+            raise NotImplementedError(_HOST_PATH % "ClassificationAccuracy.update")
+        if self.counts is None:
+            self.counts = torch.zeros(2, dtype=torch.int64, device=prediction.device)
+        targets = torch.as_tensor(targets, device=prediction.device).to(torch.int64).contiguous()
+        prediction = prediction.detach().to(torch.float32)
+        if prediction.stride(1) != 1:
+            prediction = prediction.contiguous()
+        return K.cls_accuracy_rows(prediction, targets, self.counts)[0]

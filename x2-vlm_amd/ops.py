@@ -3,7 +3,7 @@
 import torch
 
 from . import kernels as K
-from .engine import (CrossEntropyFn, GatherRowsFn, GeluF32Fn, L2NormFn, LayerNormF32Fn, LinearBf16Fn, LinearF32Fn)
+from .engine import (BANK, CrossEntropyFn, GatherRowsFn, GeluF32Fn, L2NormFn, LayerNormF32Fn, LinearBf16Fn, LinearF32Fn)
 
 
 def linear(x, w, b=None):
@@ -154,3 +154,96 @@ def cls_tail(seq, h, targets=None):
         raise NotImplementedError(_HOST_PATH % "ops.cls_tail")
     labels = None if targets is None else targets.detach().to(torch.int64).contiguous()
     return _ClsTail.apply(h, seq[1].weight, seq[1].bias, seq[3].weight, seq[3].bias, seq[1].eps, labels)
+
+
+class _ClsWide(torch.autograd.Function):
+    """LayerNorm -> GELU -> Linear(H -> C) with C in the hundreds or thousands, and one of three losses on its logits: none, the cross-entropy with
+    several weighted targets per row (entries offs[r] .. offs[r+1]-1 of targets / weights), or the KL divergence to a dense teacher.  The logits
+    are the MFMA GEMM of the bf16 activation (kernels.lngelu_fwd) with the zero-padded bf16 weight (BANK.vocab, Cp = C rounded up to 64: the pad
+    columns hold 0 and no kernel reads them); the losses, their bf16 dlogits and LayerNorm -> GELU's backward are csrc/classify_wide.hip, the input
+    and weight gradients the GEMMs the MLM decoder uses.  Kept for the backward: h, act, {mean, rstd}, the padded logits and the per-row
+    statistics; the denominator stays in `stat` on the device and nothing is read back, so the function can be captured."""
+
+    @staticmethod
+    def forward(ctx, h, gamma, beta, w, bias, eps, offs, targets, weights, teacher, denom_mode):
+        if h.stride(-1) != 1 or h.stride(0) % 4 or h.data_ptr() % 16:
+            h = h.contiguous()
+        R, C = h.shape[0], w.shape[0]
+        act, rowstat = K.lngelu_fwd(h, gamma.detach().contiguous(), beta.detach().contiguous(), eps)
+        Wp, _ = BANK.vocab(w)
+        Cp = Wp.shape[0]
+        bias_p = BANK.vector(bias, Cp - C) if Cp > C else bias.detach()
+        logits = K.gemm_nt(act, Wp, bias=bias_p, out_dtype=torch.float32)
+        lse = lse_t = stat = None
+        if teacher is not None:
+            ctx.mode = 2
+            lse, lse_t, _, stat = K.kl_ce_fwd(logits, teacher, C)
+        elif targets is not None:
+            ctx.mode = 1
+            lse, _, stat = K.soft_ce_fwd(logits, C, offs, targets, weights, denom_mode)
+        else:
+            ctx.mode = 0
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(h, gamma, beta, w, act, rowstat, logits, offs, targets, weights, teacher, lse, lse_t, stat)
+        return logits[:, :C], (stat[0] if stat is not None else None)
+
+    @staticmethod
+    def backward(ctx, g_logits, g_loss):
+        h, gamma, beta, w, act, rowstat, logits, offs, targets, weights, teacher, lse, lse_t, stat = ctx.saved_tensors
+        if g_logits is None and g_loss is None:
+            return (None,) * 11
+        BANK.note_backward()
+        R, H = h.shape
+        C = w.shape[0]
+        g_loss = None if g_loss is None else g_loss.to(torch.float32).reshape(1).contiguous()
+        g_logits = None if g_logits is None else g_logits.to(torch.float32).contiguous()
+        _, WpT = BANK.vocab(w)
+        Cp = WpT.shape[1]
+        if ctx.mode == 2:
+            dl = K.kl_ce_bwd(R, C, logits=logits, teacher=teacher, lse=lse, lse_t=lse_t, g_loss=g_loss, g_logits=g_logits, Cp=Cp)
+        elif ctx.mode == 1:
+            dl = K.soft_ce_bwd(R, C, logits=logits, offs=offs, targets=targets, weights=weights, lse=lse, stat=stat, g_loss=g_loss,
+                               g_logits=g_logits, Cp=Cp)
+        else:
+            dl = K.soft_ce_bwd(R, C, g_logits=g_logits, Cp=Cp)
+        dact = K.gemm_nt(dl, WpT, out_dtype=torch.float32)
+        dw = torch.empty_like(w)
+        K.gemm_tn_grouped([(dl, act, dw, Cp, H)])
+        dbias_p = torch.zeros(Cp, device=h.device, dtype=torch.float32)
+        K.colsum_bf16(dl, dbias_p)
+        dh, dgamma, dbeta = K.lngelu_bwd(dact, h, gamma.detach().contiguous(), beta.detach().contiguous(), rowstat)
+        return dh, dgamma, dbeta, dw, dbias_p[:C], None, None, None, None, None, None
+
+
+def cls_wide(seq, h, *, targets=None, offs=None, weights=None, teacher=None, denom_mode=0):
+    """(logits [R, C], loss | None) of a build_mlp head's tail seq[1] (LayerNorm), seq[2] (GELU), seq[3] (Linear, any number of labels) on the rows
+    h = seq[0](x).  The loss, by what is given:
+      teacher fp32 [R, C]         KLDivLoss('none')(log_softmax(logits), softmax(teacher)).sum() / R
+      targets int64 [T] with offs int32 [R + 1] (row r owns entries offs[r] .. offs[r+1]-1) and weights fp32 [T] or None (= 1):
+                                  sum_r sum_j w_j * CE(logits[r], t_j) / denom; an entry outside [0, C) (the -100 of ignore_index) is skipped;
+                                  denom_mode 0: denom = R, 1: the number of non-skipped entries (none at all gives NaN, as F.cross_entropy does)
+      neither                     None
+    Differentiable through both outputs; nothing is read back.  The caller guarantees 0 <= offs[r] <= offs[r+1] <= T."""
+    if not isinstance(h, torch.Tensor) or not h.is_cuda:
+        from .model_generation import _HOST_PATH
+        raise NotImplementedError(_HOST_PATH % "ops.cls_wide")
+    H = seq[1].weight.numel()
+    if H % 64:
+        raise ValueError("ops.cls_wide: the hidden width H=%d of the head must be a multiple of 64 (the contraction of the logits GEMM)" % H)
+    R = h.shape[0]
+    if teacher is not None:
+        teacher = teacher.detach().to(torch.float32)
+        if teacher.dim() != 2 or teacher.shape != (R, seq[3].weight.shape[0]):
+            raise ValueError("ops.cls_wide: teacher must be [R, C] = [%d, %d]" % (R, seq[3].weight.shape[0]))
+        if teacher.stride(1) != 1:
+            teacher = teacher.contiguous()
+        targets = offs = weights = None
+    elif targets is not None:
+        targets = targets.detach().to(torch.int64).contiguous().view(-1)
+        if offs is None:
+            raise ValueError("ops.cls_wide: targets need offs (int32 [R + 1])")
+        offs = offs.detach().to(torch.int32).contiguous()
+        weights = None if weights is None else weights.detach().to(torch.float32).contiguous().view(-1)
+        if offs.shape != (R + 1,) or (weights is not None and weights.shape != targets.shape):
+            raise ValueError("ops.cls_wide: offs must be [R + 1] and weights as long as targets")
+    return _ClsWide.apply(h, seq[1].weight, seq[1].bias, seq[3].weight, seq[3].bias, seq[1].eps, offs, targets, weights, teacher, denom_mode)
