@@ -115,7 +115,7 @@ def bench(args):
     dev = torch.device("cuda:0")
     out = {}
     for R, H in HEAD_SHAPES:
-        t, losses = bench_head(torch, ops, xvlm, mcl._head_first_linear, dev, R, H, args.head_steps)
+        t, losses = bench_head(torch, ops, xvlm, ops.head_first_linear, dev, R, H, args.head_steps)
         for name, (med, lo, hi) in t.items():
             out["head_%s_ms_%dx%d" % (name, R, H)] = round(med, 4)
             out["head_%s_ms_min_max_%dx%d" % (name, R, H)] = [round(lo, 4), round(hi, 4)]

@@ -11,7 +11,8 @@ mkdir -p "$OUT"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -DX2_PROBE"
 pids=()
 for f in runtime gemm attention rowwise heads masking optim comm; do
-  if [ ! -f "$OUT/$f.o" ] || [ "$SRC/$f.hip" -nt "$OUT/$f.o" ] || [ "$SRC/x2_common.h" -nt "$OUT/$f.o" ]; then
+  newest=$(ls -t "$SRC/$f.hip" "$SRC"/*.h | head -1)          # every header counts, as in csrc/build.sh
+  if [ ! -f "$OUT/$f.o" ] || [ "$newest" -nt "$OUT/$f.o" ]; then
     hipcc $FLAGS -c "$SRC/$f.hip" -o "$OUT/$f.o" &
     pids+=($!)
   fi

@@ -13,6 +13,7 @@ import torch
 
 from cases import CASES
 from cases_cls import CLS_CASES, cls_batch, cls_config
+from step_helpers import replays_match_eager
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
@@ -69,9 +70,8 @@ def test_graph_replay_is_the_eager_step(synthetic):
     assert step.mode == "hipgraph", step.error
     captured = [p.grad for p in params]                      # the arenas the graph writes on every replay
     assert all(g is not None for g in captured)
-    seen = []
-    for i, b in enumerate(data):
-        graph.GraphedStep.copy_inputs(static, b)
+
+    def reference_loss(i, b):
         # the reference's formula for THIS batch's k on the logits of the same state (the graph must not have frozen the first batch's offsets).
         # This forward comes first: the weight bank re-casts at the first forward after a backward, and the update below writes through p.data
         with torch.no_grad():
@@ -80,25 +80,11 @@ def test_graph_replay_is_the_eager_step(synthetic):
         n = sum(KS[i])
         nll = torch.nn.functional.cross_entropy(prediction[rows], b["targets"][:n].cpu(), reduction="none")
         want = float((b["weights"][:n].cpu().double() * nll).sum() / 4)
-        le = {k: float(v) for k, v in fwd_bwd().items()}     # eager launches (re-binds .grad to fresh tensors)
-        torch.cuda.synchronize()
-        eager = [p.grad.detach().clone() for p in params]
-        lg = {k: float(v) for k, v in step().items()}        # the same state through the captured graph
-        torch.cuda.synchronize()
-        for k in le:
-            assert abs(le[k] - lg[k]) <= 1e-6 * max(1.0, abs(le[k])), (i, k, le[k], lg[k])
-        total = sum(float(g.double().pow(2).sum()) for g in eager) ** 0.5
-        worst = 0.0
-        for n, ge, gg in zip(names, eager, captured):
-            assert bool(torch.isfinite(gg).all()), n
-            if "key.bias" not in n:                          # key biases: analytically zero gradient, pure rounding noise
-                err = float((ge.double() - gg.double()).norm()) / max(float(ge.double().norm()), 1e-2 * total)
-                worst = max(worst, err)
-                assert err <= 5e-3, (i, n, err)
-        assert abs(lg["loss"] - want) <= 1e-5 * want, (i, lg["loss"], want)
-        print("vqa-cls step, batch %d (k = %s): eager %s, replay %s, worst gradient tensor difference %.2e" % (i, KS[i], le, lg, worst))
-        seen.append(lg)
-        with torch.no_grad():                                # the next state, through p.data as transformers' AdamW moves it
-            for p, g in zip(params, eager):
-                p.data.add_(g, alpha=-0.02)
+
+        def check(lg):
+            print("vqa-cls step, batch %d: k = %s, reference loss %.6f" % (i, KS[i], want))
+            assert abs(lg["loss"] - want) <= 1e-5 * want, (i, lg["loss"], want)
+        return check
+
+    seen = replays_match_eager("vqa-cls step", step, fwd_bwd, static, params, names, captured, data, before=reference_loss)
     assert all(s["loss"] > 0.0 for s in seen) and len(set(s["loss"] for s in seen)) == 3

@@ -8,10 +8,10 @@ import importlib
 import tempfile
 
 import pytest
-import torch
 
 from cases import CASES
 from cases_nlvr import NLVR_CASES, nlvr_batch, nlvr_config
+from step_helpers import replays_draw_new_masks, replays_match_eager
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
@@ -56,29 +56,7 @@ def test_graph_replay_is_the_eager_step(synthetic):
     assert step.mode == "hipgraph", step.error
     captured = [p.grad for p in params]                      # the arenas the graph writes on every replay
     assert all(g is not None for g in captured)
-    seen = []
-    for i, b in enumerate(data):
-        graph.GraphedStep.copy_inputs(static, b)
-        le = {k: float(v) for k, v in fwd_bwd().items()}     # eager launches (re-binds .grad to fresh tensors)
-        torch.cuda.synchronize()
-        eager = [p.grad.detach().clone() for p in params]
-        lg = {k: float(v) for k, v in step().items()}        # the same state through the captured graph
-        torch.cuda.synchronize()
-        for k in le:
-            assert abs(le[k] - lg[k]) <= 1e-6 * max(1.0, abs(le[k])), (i, k, le[k], lg[k])
-        total = sum(float(g.double().pow(2).sum()) for g in eager) ** 0.5
-        worst = 0.0
-        for n, ge, gg in zip(names, eager, captured):
-            assert bool(torch.isfinite(gg).all()), n
-            if "key.bias" not in n:                          # key biases: analytically zero gradient, pure rounding noise
-                err = float((ge.double() - gg.double()).norm()) / max(float(ge.double().norm()), 1e-2 * total)
-                worst = max(worst, err)
-                assert err <= 5e-3, (i, n, err)
-        print("nlvr step, batch %d: eager %s, replay %s, worst gradient tensor difference %.2e" % (i, le, lg, worst))
-        seen.append(lg)
-        with torch.no_grad():                                # the next state, through p.data as transformers' AdamW moves it
-            for p, g in zip(params, eager):
-                p.data.add_(g, alpha=-0.02)
+    seen = replays_match_eager("nlvr step", step, fwd_bwd, static, params, names, captured, data)
     assert all(s["loss"] > 0.0 for s in seen) and len(set(s["loss"] for s in seen)) == 3
 
 
@@ -89,10 +67,4 @@ def test_replays_draw_new_dropout_masks(synthetic):
     params = list(model.parameters())
     step = graph.GraphedStep(_step_fn(model, static, params))
     assert step.mode == "hipgraph", step.error
-    seen = []
-    for _ in range(4):
-        loss = step()
-        seen.append(tuple(round(float(v), 6) for v in loss.values()))
-        assert all(bool(torch.isfinite(p.grad).all()) for p in params)
-    assert all(all(x == x and abs(x) < 1e4 for x in s) for s in seen)   # finite
-    assert len(set(seen)) == 4, seen                                    # same inputs, four different masks
+    replays_draw_new_masks(step, params)

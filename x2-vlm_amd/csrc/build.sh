@@ -8,7 +8,8 @@ if [ "$1" = "--clean" ]; then rm -rf ../_build $OUT; fi     # every object from 
 mkdir -p ../_build
 pids=()
 for f in runtime gemm attention rowwise heads masking optim comm decode vqa grounding classify classify_wide; do
-  if [ ! -f ../_build/$f.o ] || [ $f.hip -nt ../_build/$f.o ] || [ x2_common.h -nt ../_build/$f.o ]; then
+  newest=$(ls -t $f.hip *.h | head -1)                       # every header counts: any of them may reach any object
+  if [ ! -f ../_build/$f.o ] || [ $newest -nt ../_build/$f.o ]; then
     hipcc $FLAGS -c $f.hip -o ../_build/$f.o &
     pids+=($!)
   fi

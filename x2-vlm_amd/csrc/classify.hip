@@ -8,40 +8,20 @@
 // Replaces ops.layer_norm + ops.gelu + ops.linear + ops.cross_entropy: four launches forward and about a dozen backward (with their partial-sum
 // reductions).  H is at most 16384 and C at most 16, so this is plain fp32 VALU code; what it saves is launches and the [R, H] intermediates: nothing
 // of that size lives between forward and backward besides h itself.
-// No atomics.  Every sum has a fixed order - a thread adds its elements in index order, the 64 lanes of a wave by the xor butterfly, the four waves left
-// to right; the column sums of the backward are one thread's walk over rows 0..R-1 - so two runs give the same bits.
-// The GELU is the erf form through libm's erff / expf (not x2_common.h's fast forms: a few thousand elements per row, and the logits sum H of them).
+// No atomics.  Every sum has a fixed order (x2_rowblock.h; the column sums of the backward are one thread's walk over rows 0..R-1), so two runs
+// give the same bits.  The GELU is x2_rowblock.h's gelu_erf.
 // Sub-gradients: none - LayerNorm, erf-GELU and log-softmax are smooth.  Tie rule of the accuracy: strict >, so the lowest index of equal maxima wins.
 // Labels: [0, C) or -100 is the caller's contract; any label outside [0, C) is treated as ignored and never used as an index.  With every label
 // ignored n_valid is 0 and the loss is 0 / 0 = NaN, as F.cross_entropy gives.  NaN logits are outside x2_cls_accuracy's contract.
-#include "x2_common.h"
-#include <math.h>
+#include "x2_rowblock.h"
 
-#define CL_THREADS 256
+#define CL_THREADS ROW_THREADS
 #define CL_COLS 64               // backward launch two: columns per workgroup, and rows per staged chunk of dlogits
 #define CL_MAXR 65536
 #define CL_MAXH 16384
 #define CL_MAXC 16
-static_assert(CL_THREADS == 256, "four waves per workgroup");
 
 #define CL_ALIGNED(p) ((((uintptr_t)(p)) & 15) == 0)          // rows are read and written as float4
-
-__device__ __forceinline__ float cl_block_sum(float v, float* red) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return v;
-}
-
-__device__ __forceinline__ float cl_gelu(float y) { return 0.5f * y * (1.f + erff(y * 0.70710678118654752f)); }
-// Phi(y) + y * phi(y)
-__device__ __forceinline__ float cl_dgelu(float y) {
-  return 0.5f * (1.f + erff(y * 0.70710678118654752f)) + y * 0.3989422804014327f * expf(-0.5f * y * y);
-}
-__device__ __forceinline__ float cl_sum4(const float4& v) { return (v.x + v.y) + (v.z + v.w); }
-__device__ __forceinline__ float cl_dot4(const float4& a, const float4& b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
 
 // dlogits of one row: g_logits (or 0) + scale * (softmax(logits) - onehot(label)) on a valid row; scale = g_loss / n_valid (0 without g_loss)
 template <int CM>
@@ -81,27 +61,19 @@ __global__ __launch_bounds__(CL_THREADS) void cls_tail_fwd_kernel(const float* _
   const float4* g4 = reinterpret_cast<const float4*>(gamma);
   const float4* b4 = reinterpret_cast<const float4*>(beta);
   const float4* w4 = reinterpret_cast<const float4*>(w);
-  float s = 0.f;
-  for (int i = threadIdx.x; i < n4; i += CL_THREADS) s += cl_sum4(x4[i]);
-  const float mean = cl_block_sum(s, red) / (float)H;
-  float q = 0.f;
-  for (int i = threadIdx.x; i < n4; i += CL_THREADS) {
-    float4 v = x4[i];
-    v.x -= mean; v.y -= mean; v.z -= mean; v.w -= mean;
-    q += cl_dot4(v, v);
-  }
-  const float rstd = 1.f / sqrtf(cl_block_sum(q, red) / (float)H + eps);
+  float mean, rstd;
+  row_ln_stats(x4, n4, H, eps, red, mean, rstd);
   float acc[CM];
 #pragma unroll
   for (int c = 0; c < CM; ++c) acc[c] = 0.f;
   for (int i = threadIdx.x; i < n4; i += CL_THREADS) {
     const float4 v = x4[i], g = g4[i], b = b4[i];
     float4 a;
-    a.x = cl_gelu((v.x - mean) * rstd * g.x + b.x); a.y = cl_gelu((v.y - mean) * rstd * g.y + b.y);
-    a.z = cl_gelu((v.z - mean) * rstd * g.z + b.z); a.w = cl_gelu((v.w - mean) * rstd * g.w + b.w);
+    a.x = gelu_erf((v.x - mean) * rstd * g.x + b.x); a.y = gelu_erf((v.y - mean) * rstd * g.y + b.y);
+    a.z = gelu_erf((v.z - mean) * rstd * g.z + b.z); a.w = gelu_erf((v.w - mean) * rstd * g.w + b.w);
 #pragma unroll
     for (int c = 0; c < CM; ++c)
-      if (c < C) acc[c] += cl_dot4(a, w4[(size_t)c * n4 + i]);
+      if (c < C) acc[c] += dot4(a, w4[(size_t)c * n4 + i]);
   }
 #pragma unroll
   for (int c = 0; c < CM; ++c)
@@ -144,8 +116,8 @@ __global__ __launch_bounds__(CL_THREADS) void cls_loss_mean_kernel(const float* 
     const long lab = labels[r];
     if (lab >= 0 && lab < C) { s += nll[r]; n += 1.f; }
   }
-  s = cl_block_sum(s, red);
-  n = cl_block_sum(n, red);                           // at most 65536: exact in fp32
+  s = row_block_sum(s, red);
+  n = row_block_sum(n, red);                          // at most 65536: exact in fp32
   if (threadIdx.x == 0) {
     stat[0] = s / n;
     stat[1] = n;
@@ -211,19 +183,19 @@ __global__ __launch_bounds__(CL_THREADS) void cls_tail_bwd_rows_kernel(const flo
         da.x += dl[c] * wv.x; da.y += dl[c] * wv.y; da.z += dl[c] * wv.z; da.w += dl[c] * wv.w;
       }
     float4 d;
-    d.x = da.x * cl_dgelu(xh.x * g.x + b.x) * g.x; d.y = da.y * cl_dgelu(xh.y * g.y + b.y) * g.y;
-    d.z = da.z * cl_dgelu(xh.z * g.z + b.z) * g.z; d.w = da.w * cl_dgelu(xh.w * g.w + b.w) * g.w;
+    d.x = da.x * dgelu(xh.x * g.x + b.x) * g.x; d.y = da.y * dgelu(xh.y * g.y + b.y) * g.y;
+    d.z = da.z * dgelu(xh.z * g.z + b.z) * g.z; d.w = da.w * dgelu(xh.w * g.w + b.w) * g.w;
     return d;
   };
   float s1 = 0.f, s2 = 0.f;
   for (int i = threadIdx.x; i < n4; i += CL_THREADS) {
     float4 xh;
     const float4 d = dxhat4(i, xh);
-    s1 += cl_sum4(d);
-    s2 += cl_dot4(d, xh);
+    s1 += sum4(d);
+    s2 += dot4(d, xh);
   }
-  s1 = cl_block_sum(s1, red) / (float)H;
-  s2 = cl_block_sum(s2, red) / (float)H;
+  s1 = row_block_sum(s1, red) / (float)H;
+  s2 = row_block_sum(s2, red) / (float)H;
   for (int i = threadIdx.x; i < n4; i += CL_THREADS) {          // the same arithmetic again instead of an [H] row kept somewhere
     float4 xh;
     float4 d = dxhat4(i, xh);
@@ -278,7 +250,7 @@ __global__ __launch_bounds__(CL_COLS) void cls_tail_bwd_cols_kernel(const float*
         float da = 0.f;
 #pragma unroll
         for (int c = 0; c < CM; ++c) da += sdl[k][c] * wj[c];
-        const float dy = da * cl_dgelu(y), a = cl_gelu(y);
+        const float dy = da * dgelu(y), a = gelu_erf(y);
         dg += dy * xh;
         db += dy;
 #pragma unroll

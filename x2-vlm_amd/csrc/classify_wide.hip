@@ -13,10 +13,9 @@
 // The pad columns [C, Cp) of the logits hold 0 (zero weight rows, zero bias), not -inf: every kernel reads columns [0, C) only, and never a column
 // at or beyond C of any input (tests fill them with NaN).
 // Plain fp32 arithmetic, no atomics, libm erff / erfcf / expf / logf.  Fixed summation orders, so two runs give the same bits:
-//   a row sum      columns are taken in groups of four (group i = columns 4i .. 4i+3, missing columns contribute the neutral element); thread t adds
-//                  groups t, t + 256, ... in that order, each group as (x + y) + (z + w); the 64 lanes of a wave by the xor butterfly; the four waves
-//                  as (w0 + w1) + (w2 + w3).  Row maxima the same way (order-free anyway).  Whether a group is read as one float4 (16-byte aligned
-//                  base and a leading dimension % 4 == 0) or as four scalars does not change the arithmetic.
+//   a row sum      x2_rowblock.h's order over groups of four columns (group i = columns 4i .. 4i+3, missing columns contribute the neutral
+//                  element); row maxima the same way (order-free anyway).  Whether a group is read as one float4 (16-byte aligned base and a
+//                  leading dimension % 4 == 0) or as four scalars does not change the arithmetic.
 //   entries        rowloss, Wr and the per-column sum over duplicate targets run over the row's entries in index order (one thread; the backward
 //                  stages the entries in LDS in chunks of 256 and every column's owner walks each chunk in index order) - no maximum k.
 //   over rows      launch two of a forward: thread t adds rows t, t + 256, ... in order, then the block sum above; the non-skipped count is an
@@ -26,45 +25,19 @@
 // F.cross_entropy(ignore_index=-100) does.  A teacher probability that underflows to 0 contributes 0 (torch's xlogy rule).
 // Tie rule of the accuracy: the lowest index of bit-equal maxima wins (prediction.max(1)); NaN logits are outside the contract; a label of -100
 // (or any label that is no column) is a miss.
-#include "x2_common.h"
-#include <math.h>
+#include "x2_rowblock.h"
 #include <limits.h>
 
-#define CW_THREADS 256
+#define CW_THREADS ROW_THREADS
 #define CW_COLS 64               // lngelu backward launch two: columns per workgroup, rows per staged chunk of {mean, rstd}
 #define CW_CHUNK 256             // entries of a row staged in LDS at a time
 #define CW_MAXR 65536
 #define CW_MAXH 16384
 #define CW_MAXC (1 << 20)
-static_assert(CW_THREADS == 256 && CW_CHUNK == CW_THREADS, "four waves per workgroup; one staged entry per thread");
+static_assert(CW_CHUNK == CW_THREADS, "one staged entry per thread");
 
 #define CW_ALIGNED(p, n) ((((uintptr_t)(p)) & ((n) - 1)) == 0)
 #define CW_VEC(p, ld) (CW_ALIGNED(p, 16) && (ld) % 4 == 0)          // rows may be read as float4
-
-__device__ __forceinline__ float cw_block_sum(float v, float* red) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return v;
-}
-__device__ __forceinline__ float cw_block_max(float v, float* red) {
-  v = wave_max(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-  return v;
-}
-// y Phi(y) with Phi(y) = erfc(-y / sqrt 2) / 2: libm's erfcf keeps its relative accuracy in the negative tail, where 1 + erff(.) cancels - the
-// result is rounded to bf16, whose ulp is relative, so the tail has to be right to a relative, not an absolute, error
-__device__ __forceinline__ float cw_gelu(float y) { return 0.5f * y * erfcf(y * -0.70710678118654752f); }
-__device__ __forceinline__ float cw_dgelu(float y) {
-  return 0.5f * (1.f + erff(y * 0.70710678118654752f)) + y * 0.3989422804014327f * expf(-0.5f * y * y);
-}
-__device__ __forceinline__ float cw_sum4(const float4& v) { return (v.x + v.y) + (v.z + v.w); }
-__device__ __forceinline__ float cw_dot4(const float4& a, const float4& b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
 
 // columns 4g .. 4g+3 of a row of C readable columns; a column at or beyond C is never read and comes back as `fill`
 __device__ __forceinline__ float4 cw_load4(const float* __restrict__ row, int g, int C, bool vec, float fill) {
@@ -92,15 +65,15 @@ __device__ __forceinline__ float cw_row_lse(const float* __restrict__ row, int C
     const float4 v = cw_load4(row, g, C, vec, -INFINITY);
     m = fmaxf(m, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
   }
-  m = cw_block_max(m, red);
+  m = row_block_max(m, red);
   float s = 0.f;
   for (int g = threadIdx.x; g < ng; g += CW_THREADS) {
     const float4 v = cw_load4(row, g, C, vec, -INFINITY);           // exp(-inf - m) = 0: the neutral element of the sum
     float4 e;
     e.x = expf(v.x - m); e.y = expf(v.y - m); e.z = expf(v.z - m); e.w = expf(v.w - m);
-    s += cw_sum4(e);
+    s += sum4(e);
   }
-  s = cw_block_sum(s, red);
+  s = row_block_sum(s, red);
   return m + logf(s);
 }
 
@@ -114,21 +87,13 @@ __global__ __launch_bounds__(CW_THREADS) void lngelu_fwd_kernel(const float* __r
   const float4* g4 = reinterpret_cast<const float4*>(gamma);
   const float4* b4 = reinterpret_cast<const float4*>(beta);
   bf16_t* arow = act + (size_t)r * lda;
-  float s = 0.f;
-  for (int i = threadIdx.x; i < n4; i += CW_THREADS) s += cw_sum4(x4[i]);
-  const float mean = cw_block_sum(s, red) / (float)H;
-  float q = 0.f;
-  for (int i = threadIdx.x; i < n4; i += CW_THREADS) {
-    float4 v = x4[i];
-    v.x -= mean; v.y -= mean; v.z -= mean; v.w -= mean;
-    q += cw_dot4(v, v);
-  }
-  const float rstd = 1.f / sqrtf(cw_block_sum(q, red) / (float)H + eps);
+  float mean, rstd;
+  row_ln_stats(x4, n4, H, eps, red, mean, rstd);
   for (int i = threadIdx.x; i < n4; i += CW_THREADS) {
     const float4 v = x4[i], g = g4[i], b = b4[i];
     float4 a;
-    a.x = cw_gelu((v.x - mean) * rstd * g.x + b.x); a.y = cw_gelu((v.y - mean) * rstd * g.y + b.y);
-    a.z = cw_gelu((v.z - mean) * rstd * g.z + b.z); a.w = cw_gelu((v.w - mean) * rstd * g.w + b.w);
+    a.x = gelu_erfc((v.x - mean) * rstd * g.x + b.x); a.y = gelu_erfc((v.y - mean) * rstd * g.y + b.y);
+    a.z = gelu_erfc((v.z - mean) * rstd * g.z + b.z); a.w = gelu_erfc((v.w - mean) * rstd * g.w + b.w);
     cw_store_bf16x4(arow + 4 * i, a);
   }
   if (threadIdx.x == 0) {
@@ -174,19 +139,19 @@ __global__ __launch_bounds__(CW_THREADS) void lngelu_bwd_rows_kernel(const float
     const float4 v = x4[i], g = g4[i], b = b4[i], da = a4[i];
     xh.x = (v.x - mean) * rstd; xh.y = (v.y - mean) * rstd; xh.z = (v.z - mean) * rstd; xh.w = (v.w - mean) * rstd;
     float4 d;
-    d.x = da.x * cw_dgelu(xh.x * g.x + b.x) * g.x; d.y = da.y * cw_dgelu(xh.y * g.y + b.y) * g.y;
-    d.z = da.z * cw_dgelu(xh.z * g.z + b.z) * g.z; d.w = da.w * cw_dgelu(xh.w * g.w + b.w) * g.w;
+    d.x = da.x * dgelu(xh.x * g.x + b.x) * g.x; d.y = da.y * dgelu(xh.y * g.y + b.y) * g.y;
+    d.z = da.z * dgelu(xh.z * g.z + b.z) * g.z; d.w = da.w * dgelu(xh.w * g.w + b.w) * g.w;
     return d;
   };
   float s1 = 0.f, s2 = 0.f;
   for (int i = threadIdx.x; i < n4; i += CW_THREADS) {
     float4 xh;
     const float4 d = dxhat4(i, xh);
-    s1 += cw_sum4(d);
-    s2 += cw_dot4(d, xh);
+    s1 += sum4(d);
+    s2 += dot4(d, xh);
   }
-  s1 = cw_block_sum(s1, red) / (float)H;
-  s2 = cw_block_sum(s2, red) / (float)H;
+  s1 = row_block_sum(s1, red) / (float)H;
+  s2 = row_block_sum(s2, red) / (float)H;
   for (int i = threadIdx.x; i < n4; i += CW_THREADS) {          // the same arithmetic again instead of an [H] row kept somewhere
     float4 xh;
     float4 d = dxhat4(i, xh);
@@ -220,7 +185,7 @@ __global__ __launch_bounds__(CW_COLS) void lngelu_bwd_cols_kernel(const float* _
 #pragma unroll 4
       for (int k = 0; k < nr; ++k) {
         const float xh = (col[(size_t)k * ldh] - smean[k]) * srstd[k];
-        const float dy = dcol[(size_t)k * ldd] * cw_dgelu(xh * gam + bet);
+        const float dy = dcol[(size_t)k * ldd] * dgelu(xh * gam + bet);
         dg += dy * xh;
         db += dy;
       }
@@ -278,7 +243,7 @@ __global__ __launch_bounds__(CW_THREADS) void soft_ce_mean_kernel(const float* _
   __shared__ int ired[CW_THREADS / 64];
   float s = 0.f;
   for (int r = threadIdx.x; r < R; r += CW_THREADS) s += rowloss[r];
-  s = cw_block_sum(s, red);
+  s = row_block_sum(s, red);
   float denom = (float)R;
   if (denom_mode == 1) {
     int n = 0;
@@ -336,9 +301,9 @@ __global__ __launch_bounds__(CW_THREADS) void kl_ce_rows_kernel(const float* __r
     const float4 t = cw_load4(trow, g, C, vect != 0, -INFINITY), z = cw_load4(zrow, g, C, vec != 0, 0.f);
     float4 k;
     k.x = term(t.x, z.x); k.y = term(t.y, z.y); k.z = term(t.z, z.z); k.w = term(t.w, z.w);
-    s += cw_sum4(k);
+    s += sum4(k);
   }
-  s = cw_block_sum(s, red);
+  s = row_block_sum(s, red);
   if (threadIdx.x == 0) {
     lse[r] = lz;
     lse_t[r] = lt;

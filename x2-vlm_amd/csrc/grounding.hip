@@ -4,8 +4,8 @@
 //   x2_grounding_iou   grounding_eval_bbox / computeIoU (dataset/utils.py:363-453) of a whole evaluation set, one launch
 // Replaces XVLMBase.get_bbox_loss + box_ops.py (xvlm.py:927-957): about forty elementwise ATen launches forward and as many in autograd's
 // backward.  The work is a few flops per row, so this is plain VALU code; what it saves is launches and the host sync of the early-out.
-// No atomics: the forward is ONE workgroup (the flag and the means need every row; thread t adds rows t, t + 256, ... in index order, the 64
-// lanes of a wave by the xor butterfly, the four waves left to right), so two runs give the same bits.
+// No atomics: the forward is ONE workgroup (the flag and the means need every row; thread t adds rows t, t + 256, ... in index order, then
+// x2_rowblock.h's block sum), so two runs give the same bits.
 //
 // Sub-gradient choices of the backward (the reference's autograd splits a tie of max / min in half; tests stay away from ties):
 //   |coord - target| at 0 -> 0 (as torch);  max(a, b) / min(a, b) at a == b -> the gradient goes to the TARGET's edge, the prediction gets 0;
@@ -13,13 +13,11 @@
 // Degenerate flag: some row of either box set has x2 < x1 or y2 < y1 after cx +- 0.5 * w (rows with keep == 0 count, as in the reference):
 // every row's GIoU term is 0 and the backward does not evaluate a single GIoU expression, so no 0 / 0 of an unselected branch can reach
 // dlogits.  Without the flag the arithmetic is the reference's: a pair of zero-area boxes (union 0) is NaN there and here.
-#include "x2_common.h"
-#include <math.h>
+#include "x2_rowblock.h"
 
-#define GR_THREADS 256
+#define GR_THREADS ROW_THREADS
 #define GR_MAXB (1 << 20)          // forward: one workgroup walks every row (4096 rows per thread at the limit)
 #define GR_MAXN (1 << 24)
-static_assert(GR_THREADS == 256, "four waves per workgroup");
 
 #define GR_ALIGNED(p) ((((uintptr_t)(p)) & 15) == 0)          // rows of four floats are read and written as float4
 
@@ -41,15 +39,6 @@ __device__ __forceinline__ float gr_giou_loss(const GrBox& a, const GrBox& b) {
   return 1.f - (inter / uni - (area - uni) / area);
 }
 
-__device__ __forceinline__ float gr_block_sum(float v, float* red) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return v;
-}
-
 __global__ __launch_bounds__(GR_THREADS) void bbox_loss_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ target,
                                                                    const float* __restrict__ keep, int B, float* __restrict__ coord,
                                                                    float* __restrict__ stat) {
@@ -68,10 +57,10 @@ __global__ __launch_bounds__(GR_THREADS) void bbox_loss_fwd_kernel(const float* 
     if (!deg) gi += gr_giou_loss(a, b) * k;          // a degenerate row sets the flag: its own term is never needed
     num += k;
   }
-  l1 = gr_block_sum(l1, red);
-  gi = gr_block_sum(gi, red);
-  bad = gr_block_sum(bad, red);
-  num = keep ? gr_block_sum(num, red) : (float)B;
+  l1 = row_block_sum(l1, red);
+  gi = row_block_sum(gi, red);
+  bad = row_block_sum(bad, red);
+  num = keep ? row_block_sum(num, red) : (float)B;
   if (threadIdx.x == 0) {
     const bool flag = bad > 0.f;
     stat[0] = l1 / num;

@@ -6,35 +6,16 @@
 // the result does not depend on how the work is split.  No atomics: every output element has one writer.  The work is tiny (k <= 256
 // per question); what these kernels save is launches, the per-question host loop and the [B * k, La, La] 0/1 mask, so they are plain
 // VALU code with one workgroup per question (candidates: per row).
-#include "x2_common.h"
-#include <math.h>
+#include "x2_rowblock.h"
 
-#define VQ_THREADS 256
+#define VQ_THREADS ROW_THREADS
 #define VQ_MAXK 256
 #define VQ_MAXNA 65536
 #define VQ_MAXLA 128
 #define VQ_CACHE 8192          // candidates whose log-probability is kept in LDS between the selection rounds (the rest are recomputed)
-static_assert(VQ_THREADS == 256 && VQ_MAXK <= VQ_THREADS, "four waves per workgroup, one thread per selected slot");
+static_assert(VQ_MAXK <= VQ_THREADS, "one thread per selected slot");
 
 __device__ __forceinline__ bool vq_better(float av, int ac, float bv, int bc) { return av > bv || (av == bv && ac < bc); }
-
-// max over the workgroup (four waves); red: 4 floats of LDS, reusable after the call
-__device__ __forceinline__ float vq_block_max(float v, float* red) {
-  v = wave_max(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-  return v;
-}
-__device__ __forceinline__ float vq_block_sum(float v, float* red) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------- first stage
 // One workgroup per question row.  logp[c] = (z[first_tok[c]] - max) - log(sum exp(z - max)) over the V valid columns (x2_logprob_topk's
@@ -49,10 +30,10 @@ __global__ __launch_bounds__(VQ_THREADS) void answer_topk_kernel(const float* __
   const float* x = logits + (size_t)row * ldv;
   float m = -INFINITY;
   for (int c = tid; c < V; c += VQ_THREADS) m = fmaxf(m, x[c]);
-  m = vq_block_max(m, sRedF);
+  m = row_block_max(m, sRedF);
   float sum = 0.f;
   for (int c = tid; c < V; c += VQ_THREADS) sum += expf(x[c] - m);
-  const float lsum = logf(vq_block_sum(sum, sRedF));
+  const float lsum = logf(row_block_sum(sum, sRedF));
   auto logp = [&](int c) -> float {
     const int t = first_tok[c];
     return (unsigned)t < (unsigned)V ? (x[t] - m) - lsum : -INFINITY;
@@ -158,9 +139,9 @@ __global__ __launch_bounds__(VQ_THREADS) void vqa_rerank_kernel(const float* __r
     scores[(size_t)b * K + j] = sc;
     sScore[j] = sc;
   }
-  const float mx = vq_block_max(sc, sRed);                                 // the barrier inside also publishes sScore
+  const float mx = row_block_max(sc, sRed);                                // the barrier inside also publishes sScore
   const float e = live ? expf(sc - mx) : 0.f;
-  const float den = vq_block_sum(e, sRed);
+  const float den = row_block_sum(e, sRed);
   if (live) {
     int rank = 0;
     for (int i = 0; i < K; ++i) rank += vq_better(sScore[i], i, sc, j) ? 1 : 0;

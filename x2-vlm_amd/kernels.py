@@ -964,6 +964,19 @@ def _box_rows(t, name):
     return t.shape[0]
 
 
+# conditions that several wrappers below assert: a loss's cotangent as a device scalar, one label per row, the accuracy kernels' {correct, rows}
+def _is_dev_scalar(g, dev):
+    return g.dtype == F32 and g.numel() == 1 and g.device == dev
+
+
+def _is_row_labels(labels, R):
+    return labels.dtype == torch.int64 and labels.shape == (R,) and labels.is_contiguous()
+
+
+def _is_hit_counts(counts, dev):
+    return counts.dtype == torch.int64 and counts.shape == (2,) and counts.is_contiguous() and counts.device == dev
+
+
 def bbox_loss_fwd(logits, target, keep=None):
     """The box tail in one launch: logits / target fp32 [B, 4] (target cxcywh), keep fp32 [B] or None -> (coord fp32 [B, 4] = sigmoid(logits),
     stat fp32 [4] = {loss_bbox, loss_giou, degenerate flag, num}).  No host round trip: the reference's early-out is the device flag."""
@@ -982,7 +995,7 @@ def bbox_loss_bwd(coord, target, keep, stat, g_bbox=None, g_giou=None, g_coord=N
     assert _box_rows(target, "target") == B and stat.dtype == F32 and stat.numel() == 4 and stat.is_contiguous()
     assert keep is None or (keep.dtype == F32 and keep.shape == (B,) and keep.is_contiguous())
     for g in (g_bbox, g_giou):
-        assert g is None or (g.dtype == F32 and g.numel() == 1 and g.device == coord.device)
+        assert g is None or _is_dev_scalar(g, coord.device)
     assert g_coord is None or _box_rows(g_coord, "g_coord") == B
     dlogits = torch.empty_like(coord)
     call("x2_bbox_loss_bwd", ptr(coord), ptr(target), ptr(keep), ptr(stat), ptr(g_bbox), ptr(g_giou), ptr(g_coord), B, ptr(dlogits))
@@ -1015,7 +1028,7 @@ def cls_tail_fwd(h, gamma, beta, w, bias, eps, labels=None):
     """LayerNorm(eps) -> erf-GELU -> Linear(H -> C) [-> cross_entropy(ignore_index=-100)] of fp32 rows h [R, H] (row stride >= H) in at most two
     launches -> (logits fp32 [R, C], rowstat fp32 [R, 2] = {mean, rstd}, nll fp32 [R] | None, stat fp32 [2] = {loss, n_valid} | None)."""
     R, H, C = _cls_rows(h, gamma, beta, w, bias)
-    assert labels is None or (labels.dtype == torch.int64 and labels.shape == (R,) and labels.is_contiguous())
+    assert labels is None or _is_row_labels(labels, R)
     logits = torch.empty(R, C, device=h.device, dtype=F32)
     rowstat = torch.empty(R, 2, device=h.device, dtype=F32)
     nll = stat = None
@@ -1032,7 +1045,7 @@ def cls_tail_bwd(h, gamma, beta, w, rowstat, logits, labels=None, stat=None, g_l
     R, H = h.shape
     C = w.shape[0]
     assert rowstat.shape == (R, 2) and logits.shape == (R, C) and rowstat.is_contiguous() and logits.is_contiguous()
-    assert g_loss is None or (g_loss.dtype == F32 and g_loss.numel() == 1 and g_loss.device == h.device and labels is not None and stat is not None)
+    assert g_loss is None or (_is_dev_scalar(g_loss, h.device) and labels is not None and stat is not None)
     assert g_logits is None or (g_logits.dtype == F32 and g_logits.shape == (R, C) and g_logits.is_contiguous())
     dh = torch.empty(R, H, device=h.device, dtype=F32)
     small = torch.empty(2 * H + C * H + C, device=h.device, dtype=F32)
@@ -1045,8 +1058,8 @@ def cls_tail_bwd(h, gamma, beta, w, rowstat, logits, labels=None, stat=None, g_l
 def cls_accuracy(logits, labels, counts):
     """pred int32 [R] = the lowest index of each row's maximum; counts int64 [2] += {rows with pred == label, R} (one launch, no read-back)."""
     R, C = logits.shape
-    assert logits.dtype == F32 and logits.is_contiguous() and labels.dtype == torch.int64 and labels.shape == (R,) and labels.is_contiguous()
-    assert counts.dtype == torch.int64 and counts.shape == (2,) and counts.is_contiguous() and counts.device == logits.device
+    assert logits.dtype == F32 and logits.is_contiguous() and _is_row_labels(labels, R)
+    assert _is_hit_counts(counts, logits.device)
     pred = torch.empty(R, device=logits.device, dtype=torch.int32)
     call("x2_cls_accuracy", ptr(logits), ptr(labels), R, C, ptr(pred), ptr(counts))
     return pred
@@ -1143,7 +1156,7 @@ def soft_ce_bwd(R, C, *, logits=None, offs=None, targets=None, weights=None, lse
     if g_loss is not None:
         ldl = _f32_rows(logits, C, "logits")
         targets, weights = _entries(R, offs, targets, weights, dev)
-        assert g_loss.dtype == F32 and g_loss.numel() == 1 and g_loss.device == dev and lse.shape == (R,) and stat.shape == (2,)
+        assert _is_dev_scalar(g_loss, dev) and lse.shape == (R,) and stat.shape == (2,)
     call("x2_soft_ce_bwd", ptr(logits), ldl, R, C, ptr(offs), ptr(targets), ptr(weights), ptr(lse), ptr(stat), ptr(g_loss), ptr(g_logits), ldg,
          ptr(dl), _rows(dl), Cp)
     return dl
@@ -1156,7 +1169,7 @@ def kl_ce_bwd(R, C, *, logits=None, teacher=None, lse=None, lse_t=None, g_loss=N
     ldl = ldt = 0
     if g_loss is not None:
         ldl, ldt = _f32_rows(logits, C, "logits"), _f32_rows(teacher, C, "teacher")
-        assert g_loss.dtype == F32 and g_loss.numel() == 1 and g_loss.device == dev and lse.shape == (R,) and lse_t.shape == (R,)
+        assert _is_dev_scalar(g_loss, dev) and lse.shape == (R,) and lse_t.shape == (R,)
     call("x2_kl_ce_bwd", ptr(logits), ldl, ptr(teacher), ldt, R, C, ptr(lse), ptr(lse_t), ptr(g_loss), ptr(g_logits), ldg, ptr(dl), _rows(dl), Cp)
     return dl
 
@@ -1167,8 +1180,8 @@ def cls_accuracy_rows(logits, labels, counts, C=None):
     R = logits.shape[0]
     C = logits.shape[1] if C is None else C
     ldl = _f32_rows(logits, C, "logits")
-    assert labels.dtype == torch.int64 and labels.shape == (R,) and labels.is_contiguous()
-    assert counts.dtype == torch.int64 and counts.shape == (2,) and counts.is_contiguous() and counts.device == logits.device
+    assert _is_row_labels(labels, R)
+    assert _is_hit_counts(counts, logits.device)
     out = torch.empty(2, R, device=logits.device, dtype=torch.int32)
     call("x2_cls_accuracy_rows", ptr(logits), ldl, ptr(labels), R, C, ptr(out[0]), ptr(out[1]), ptr(counts))
     return out[0], out[1]

@@ -27,7 +27,6 @@ import torch
 
 from . import ops
 from . import kernels as K
-from .model_generation import _HOST_PATH
 from .xvlm import XVLMBase, build_mlp
 
 
@@ -57,25 +56,10 @@ class XVLMForNLVR(XVLMBase):
         return out
 
     def forward(self, image, text_ids, text_atts, targets, train=True):
-        if not isinstance(image, torch.Tensor) or not image.is_cuda:
-            raise NotImplementedError(_HOST_PATH % "XVLMForNLVR.forward")
+        ops.require_hip(image, "XVLMForNLVR.forward")
         x = self._pair_cls(image, text_ids, text_atts)
-        head = self.cls_head
-        w0 = head[0].weight
-        if w0.shape[1] % 64 == 0 and w0.shape[0] % 8 == 0 and x.numel() % 4 == 0:          # ops.mlp_head's rule for its first Linear
-            h = ops.LinearBf16Fn.apply(x, w0, head[0].bias)
-        else:
-            h = ops.linear(x, w0, head[0].bias)
-        prediction, loss = ops.cls_tail(head, h, targets if train else None)
+        prediction, loss = ops.cls_tail(self.cls_head, ops.head_first_linear(self.cls_head, x), targets if train else None)
         return loss if train else prediction
-
-
-def _head_first_linear(head, x):
-    """cls_head[0] as XVLMForNLVR.forward runs it: ops.mlp_head's rule for its first Linear"""
-    w0 = head[0].weight
-    if w0.shape[1] % 64 == 0 and w0.shape[0] % 8 == 0 and x.numel() % 4 == 0:
-        return ops.LinearBf16Fn.apply(x, w0, head[0].bias)
-    return ops.linear(x, w0, head[0].bias)
 
 
 class XVLMForClassification(XVLMBase):
@@ -90,8 +74,7 @@ class XVLMForClassification(XVLMBase):
 
     def forward(self, image, text_ids, text_atts, targets=None, train=True):
         probe = text_ids if image is None else image
-        if not isinstance(probe, torch.Tensor) or not probe.is_cuda:
-            raise NotImplementedError(_HOST_PATH % "XVLMForClassification.forward")
+        ops.require_hip(probe, "XVLMForClassification.forward")
         if self.num_labels == 1:
             raise NotImplementedError("XVLMForClassification: the MSE regression head (num_labels == 1) is not built on the HIP path")
         if image is None:
@@ -102,7 +85,7 @@ class XVLMForClassification(XVLMBase):
         else:
             image_embeds, image_atts = self.get_vision_embeds(image)
             output_cls = self.get_cross_embeds(image_embeds, image_atts, text_ids=text_ids, text_atts=text_atts)[:, 0, :]
-        h = _head_first_linear(self.cls_head, output_cls)
+        h = ops.head_first_linear(self.cls_head, output_cls)
         if self.num_labels <= 16:
             prediction, loss = ops.cls_tail(self.cls_head, h, targets if train else None)
         elif train:
@@ -141,13 +124,12 @@ class XVLMForVQAClassification(XVLMBase):
         return torch.tensor(offs, dtype=torch.int32).to(device)
 
     def forward(self, image, text_ids, text_atts, targets=None, k=None, weights=None, train=True, answer_pred=None, return_logits=False):
-        if not isinstance(image, torch.Tensor) or not image.is_cuda:
-            raise NotImplementedError(_HOST_PATH % "XVLMForVQAClassification.forward")
+        ops.require_hip(image, "XVLMForVQAClassification.forward")
         if self.num_labels <= 16:
             raise ValueError("XVLMForVQAClassification: num_labels=%d; the wide head serves more than 16 labels" % self.num_labels)
         image_embeds, image_atts = self.get_vision_embeds(image)
         output_cls = self.get_cross_embeds(image_embeds, image_atts, text_ids=text_ids, text_atts=text_atts)[:, 0, :]
-        h = _head_first_linear(self.cls_head, output_cls)
+        h = ops.head_first_linear(self.cls_head, output_cls)
         if not train:
             return ops.cls_wide(self.cls_head, h)[0]
         if answer_pred is not None:
@@ -166,17 +148,23 @@ class NLVRAccuracy:
     then counts += {correct, rows} on the device), result() reads the two counters back once.  correct / counted equals the reference's
     metric_logger global average sum(acc_b * n_b) / sum(n_b), and is formatted as NLVR.py:96 does."""
 
+    who = "NLVRAccuracy.update"          # the name a refused host tensor is reported under
+    strided_ok = False          # whether the kernel reads a column view of wider rows in place
+
     def __init__(self):
         self.counts = None
 
+    def _launch(self, prediction, targets):
+        return K.cls_accuracy(prediction, targets, self.counts)
+
     def update(self, prediction, targets):
         """prediction fp32 [B, C] (a HIP tensor: the model's train=False output), targets [B] -> pred_class int32 [B] (left on the device)"""
-        if not isinstance(prediction, torch.Tensor) or not prediction.is_cuda:
-            raise NotImplementedError(_HOST_PATH % "NLVRAccuracy.update")
+        ops.require_hip(prediction, self.who)
         if self.counts is None:
             self.counts = torch.zeros(2, dtype=torch.int64, device=prediction.device)
         targets = torch.as_tensor(targets, device=prediction.device).to(torch.int64).contiguous()
-        return K.cls_accuracy(prediction.detach().to(torch.float32).contiguous(), targets, self.counts)
+        prediction = prediction.detach().to(torch.float32)
+        return self._launch(prediction if self.strided_ok and prediction.stride(1) == 1 else prediction.contiguous(), targets)
 
     def result(self):
         """{'acc': correct / counted} (the one read-back); printed as the reference prints its averaged stats"""
@@ -195,14 +183,8 @@ class ClassificationAccuracy(NLVRAccuracy):
     index of the row's maximum, a second launch adds {correct, rows} to the device counters; a target of -100 counts as a miss, as
     (targets == pred_class).sum() / targets.size(0) does.  result() / formatted() are NLVRAccuracy's."""
 
-    def update(self, prediction, targets):
-        """prediction fp32 [B, C] (a HIP tensor; a column view of wider rows is read in place), targets [B] -> pred_class int32 [B]"""
-        if not isinstance(prediction, torch.Tensor) or not prediction.is_cuda:
-            raise NotImplementedError(_HOST_PATH % "ClassificationAccuracy.update")
-        if self.counts is None:
-            self.counts = torch.zeros(2, dtype=torch.int64, device=prediction.device)
-        targets = torch.as_tensor(targets, device=prediction.device).to(torch.int64).contiguous()
-        prediction = prediction.detach().to(torch.float32)
-        if prediction.stride(1) != 1:
-            prediction = prediction.contiguous()
+    who = "ClassificationAccuracy.update"
+    strided_ok = True
+
+    def _launch(self, prediction, targets):
         return K.cls_accuracy_rows(prediction, targets, self.counts)[0]

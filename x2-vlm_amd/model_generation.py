@@ -18,11 +18,9 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
+from . import ops
 from .xbert import BertLMHeadModel
 from .xvlm import XVLMBase
-
-
-_HOST_PATH = "%s runs on the HIP path; a host (CPU) path is a possible follow-up and is not implemented"
 
 
 @contextlib.contextmanager
@@ -135,8 +133,7 @@ class XVLMForMLMCaptioning(XVLMBase):
         Sizes as the reference (model_generation.py:113-127): length = input_ids.size(0) + max_length - the BATCH size, not the prompt
         length - so the search runs bsz + max_length - len(prompt_ids) steps.  Kept as it is (the goldens come from the real reference);
         like the reference there is no early exit when every beam has ended."""
-        if not isinstance(image, torch.Tensor) or not image.is_cuda:
-            raise NotImplementedError(_HOST_PATH % "generate")
+        ops.require_hip(image, "generate")
         from . import decode
         dev, batch = image.device, image.shape[0]
         prompt = torch.tensor([self.prompt_ids] * batch, dtype=torch.long, device=dev)
@@ -167,8 +164,7 @@ class XVLMForMLMCaptioning(XVLMBase):
         selections - the total scores and the ids such a run returns mean nothing (a forced id outside its parent's K candidates scores NaN); _return_traces adds a dict with, per step, the [S, K] values and ids of x2_logprob_topk, the [S, V] log-scores when
         V <= 1024 and the [MASK]-row logits, plus the [T, B, K] total_scores / step_ids / back_ptrs; _use_cache=False recomputes the whole
         prefix every step through the full-sequence forward (the measured baseline)."""
-        if not isinstance(image, torch.Tensor) or not image.is_cuda:
-            raise NotImplementedError(_HOST_PATH % "beam_search")
+        ops.require_hip(image, "beam_search")
         self.generation_token_ids()
         from . import decode
         with _inference(self):
@@ -266,8 +262,7 @@ class XVLMForVQA(XVLMBase):
         if train:
             raise NotImplementedError("XVLMForVQA.forward(train=True): the VQA training step (weighted per-sequence LM loss and its backward) "
                                       "is the follow-up to answer ranking and is not implemented")
-        if not isinstance(image, torch.Tensor) or not image.is_cuda:
-            raise NotImplementedError(_HOST_PATH % "XVLMForVQA.forward")
+        ops.require_hip(image, "XVLMForVQA.forward")
         with _inference(self):
             image_embeds, image_atts = self.get_vision_embeds(image)
             question_states = self.text_encoder(quesiton.input_ids, attention_mask=quesiton.attention_mask, encoder_hidden_states=image_embeds,
@@ -283,8 +278,7 @@ class XVLMForVQA(XVLMBase):
         candidate bookkeeping in torch (the measured baseline of probes/bench_vqa_rank.py); _stage1_ids int [B, k] replaces the first stage's
         selection (their log-probabilities are looked up); _return_traces adds a dict: logits0 [B, V], logp_first [B, Na], stage1_logp /
         stage1_ids [B, k], loss_rows [S, La - 1], scores [B, k] in stage-1 slot order."""
-        if not isinstance(question_states, torch.Tensor) or not question_states.is_cuda:
-            raise NotImplementedError(_HOST_PATH % "XVLMForVQA.rank_answer")
+        ops.require_hip(question_states, "XVLMForVQA.rank_answer")
         with _inference(self):
             return self._rank_answer(question_states, question_atts, answer_ids, answer_atts, int(k), _fused, _stage1_ids, _return_traces)
 

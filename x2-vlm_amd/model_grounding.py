@@ -13,7 +13,6 @@ import torch
 
 from . import checkpoint, ops
 from . import kernels as K
-from .model_generation import _HOST_PATH
 from .xvlm import XVLMBase
 
 SPLITS = ("val", "testA", "testB")
@@ -38,8 +37,7 @@ class XVLMForGrounding(XVLMBase):
         return msg
 
     def forward(self, image, text_ids, text_atts, target_bbox=None):
-        if not isinstance(image, torch.Tensor) or not image.is_cuda:
-            raise NotImplementedError(_HOST_PATH % "XVLMForGrounding.forward")
+        ops.require_hip(image, "XVLMForGrounding.forward")
         image_embeds, _ = self.get_vision_embeds(image)
         text_embeds = self.get_text_embeds(text_ids, text_atts)
         if target_bbox is None:
@@ -50,7 +48,7 @@ class XVLMForGrounding(XVLMBase):
         return ops.bbox_loss(ops.mlp_head(self.bbox_head, cls), target_bbox)
 
 
-def _f32_rows(t, cols, device=None):
+def _as_f32_rows(t, cols, device=None):
     t = torch.as_tensor(t, dtype=torch.float32, device=device).reshape(-1, cols)
     return t.contiguous()
 
@@ -58,10 +56,9 @@ def _f32_rows(t, cols, device=None):
 def grounding_iou(pred, ref_box, size):
     """pred [N, 4] normalised cxcywh (a HIP tensor: the model's output_coord rows), ref_box [N, 4] pixel xywh, size [N, 2] (width, height)
     -> (iou fp32 [N], hit bool [N] = iou >= 0.5), grounding_eval_bbox's arithmetic and computeIoU's convention, on the device."""
-    if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
-        raise NotImplementedError(_HOST_PATH % "grounding_iou")
-    pred = _f32_rows(pred.detach(), 4)
-    iou, hit = K.grounding_iou(pred, _f32_rows(ref_box, 4, pred.device), _f32_rows(size, 2, pred.device))
+    ops.require_hip(pred, "grounding_iou")
+    pred = _as_f32_rows(pred.detach(), 4)
+    iou, hit = K.grounding_iou(pred, _as_f32_rows(ref_box, 4, pred.device), _as_f32_rows(size, 2, pred.device))
     return iou, hit.bool()
 
 

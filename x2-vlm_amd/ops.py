@@ -30,6 +30,14 @@ def gather_rows(src, idx):
     return GatherRowsFn.apply(src, idx.to(torch.int32))
 
 
+_HOST_PATH = "%s runs on the HIP path; a host (CPU) path is a possible follow-up and is not implemented"
+
+
+def require_hip(t, who):
+    """the entry points without a host path: anything but a HIP tensor is refused under the caller's name"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda: raise NotImplementedError(_HOST_PATH % who)
+
+
 def mlp_head(seq, x):
     """nn.Sequential(Linear, LayerNorm(1e-5), GELU, Linear) of xvlm.py:163-169 on fp32 rows."""
     w0 = seq[0].weight
@@ -39,6 +47,15 @@ def mlp_head(seq, x):
         h = linear(x, w0, seq[0].bias)
     h = gelu(layer_norm(h, seq[1].weight, seq[1].bias, seq[1].eps))
     return linear(h, seq[3].weight, seq[3].bias)
+
+
+def head_first_linear(seq, x):
+    """seq[0] of a build_mlp head, for the heads whose tail is cls_tail / cls_wide.  The condition is mlp_head's, word for word, and the two
+    copies must change together; folding mlp_head onto this function is pending (it is on the pretraining step's path)."""
+    w0 = seq[0].weight
+    if w0.shape[1] % 64 == 0 and w0.shape[0] % 8 == 0 and x.numel() % 4 == 0:
+        return LinearBf16Fn.apply(x, w0, seq[0].bias)
+    return linear(x, w0, seq[0].bias)
 
 
 class _MaskedMeanToken0(torch.autograd.Function):
@@ -119,6 +136,17 @@ def bbox_loss(logits, target, is_image=None):
     return _BboxLoss.apply(logits, target, keep)
 
 
+def _head_rows(h):
+    """h as the row kernels read it: unit column stride, a row stride that is a multiple of 4, a 16-byte aligned base"""
+    return h.contiguous() if h.stride(-1) != 1 or h.stride(0) % 4 or h.data_ptr() % 16 else h
+
+
+def _head_cotangents(g_loss, g_logits):
+    """(g_loss as a device scalar fp32 [1], g_logits as contiguous fp32), None staying None"""
+    return (None if g_loss is None else g_loss.to(torch.float32).reshape(1).contiguous(),
+            None if g_logits is None else g_logits.to(torch.float32).contiguous())
+
+
 class _ClsTail(torch.autograd.Function):
     """LayerNorm -> GELU -> Linear(H -> C) [-> F.cross_entropy(ignore_index=-100)] behind a head's first Linear as kernels.cls_tail_fwd /
     _bwd: at most two launches each way.  Only h, the logits and the per-row {mean, rstd} are kept for the backward; n_valid stays in `stat` on
@@ -126,8 +154,7 @@ class _ClsTail(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, gamma, beta, w, bias, eps, labels):
-        if h.stride(-1) != 1 or h.stride(0) % 4 or h.data_ptr() % 16:
-            h = h.contiguous()
+        h = _head_rows(h)
         logits, rowstat, _, stat = K.cls_tail_fwd(h, gamma.detach().contiguous(), beta.detach().contiguous(), w.detach().contiguous(),
                                                   bias.detach().contiguous(), eps, labels)
         ctx.set_materialize_grads(False)
@@ -139,8 +166,7 @@ class _ClsTail(torch.autograd.Function):
         h, gamma, beta, w, rowstat, logits, labels, stat = ctx.saved_tensors
         if g_logits is None and g_loss is None:
             return (None,) * 7
-        g_loss = None if g_loss is None else g_loss.to(torch.float32).reshape(1).contiguous()
-        g_logits = None if g_logits is None else g_logits.to(torch.float32).contiguous()
+        g_loss, g_logits = _head_cotangents(g_loss, g_logits)
         dh, dgamma, dbeta, dw, dbias = K.cls_tail_bwd(h, gamma.detach().contiguous(), beta.detach().contiguous(), w.detach().contiguous(), rowstat,
                                                       logits, labels, stat, g_loss, g_logits)
         return dh, dgamma, dbeta, dw, dbias, None, None
@@ -149,9 +175,7 @@ class _ClsTail(torch.autograd.Function):
 def cls_tail(seq, h, targets=None):
     """(logits [R, C], loss | None) of a build_mlp head's tail seq[1] (LayerNorm), seq[2] (GELU), seq[3] (Linear) on the rows h = seq[0](x), the
     loss being F.cross_entropy(logits, targets, ignore_index=-100) when targets are given.  Differentiable through both outputs."""
-    if not isinstance(h, torch.Tensor) or not h.is_cuda:
-        from .model_generation import _HOST_PATH
-        raise NotImplementedError(_HOST_PATH % "ops.cls_tail")
+    require_hip(h, "ops.cls_tail")
     labels = None if targets is None else targets.detach().to(torch.int64).contiguous()
     return _ClsTail.apply(h, seq[1].weight, seq[1].bias, seq[3].weight, seq[3].bias, seq[1].eps, labels)
 
@@ -166,8 +190,7 @@ class _ClsWide(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, gamma, beta, w, bias, eps, offs, targets, weights, teacher, denom_mode):
-        if h.stride(-1) != 1 or h.stride(0) % 4 or h.data_ptr() % 16:
-            h = h.contiguous()
+        h = _head_rows(h)
         R, C = h.shape[0], w.shape[0]
         act, rowstat = K.lngelu_fwd(h, gamma.detach().contiguous(), beta.detach().contiguous(), eps)
         Wp, _ = BANK.vocab(w)
@@ -195,8 +218,7 @@ class _ClsWide(torch.autograd.Function):
         BANK.note_backward()
         R, H = h.shape
         C = w.shape[0]
-        g_loss = None if g_loss is None else g_loss.to(torch.float32).reshape(1).contiguous()
-        g_logits = None if g_logits is None else g_logits.to(torch.float32).contiguous()
+        g_loss, g_logits = _head_cotangents(g_loss, g_logits)
         _, WpT = BANK.vocab(w)
         Cp = WpT.shape[1]
         if ctx.mode == 2:
@@ -224,9 +246,7 @@ def cls_wide(seq, h, *, targets=None, offs=None, weights=None, teacher=None, den
                                   denom_mode 0: denom = R, 1: the number of non-skipped entries (none at all gives NaN, as F.cross_entropy does)
       neither                     None
     Differentiable through both outputs; nothing is read back.  The caller guarantees 0 <= offs[r] <= offs[r+1] <= T."""
-    if not isinstance(h, torch.Tensor) or not h.is_cuda:
-        from .model_generation import _HOST_PATH
-        raise NotImplementedError(_HOST_PATH % "ops.cls_wide")
+    require_hip(h, "ops.cls_wide")
     H = seq[1].weight.numel()
     if H % 64:
         raise ValueError("ops.cls_wide: the hidden width H=%d of the head must be a multiple of 64 (the contraction of the logits GEMM)" % H)
