@@ -184,55 +184,93 @@ extern "C" int x2_reduce_partials(const float* part, int nblk, int nk, int width
 struct ReduceDesc { const float* part; float* o[4]; int nblk, nk, width, blk0; };
 struct ReduceGroup { ReduceDesc d[RPM_MAX]; int count; };
 // Thread mapping: 4 column groups of 4 floats (one 16-column tile = one 64-byte segment per partial row and workgroup) x 64 row
-// slices; a thread walks the partial rows b = slice, slice + 64, ... with 16-byte loads, four in flight; the 64 slices are
-// added in a fixed order through LDS.  The reduction is a latency chain, not a bandwidth problem (a few MB per launch): what
-// counts is how few dependent load batches a thread issues and how many CUs take part - with 64-column tiles and 16 slices a
-// 788-row LayerNorm workspace was 12 batches deep on 36 workgroups (11.6 us for 7.3 MB; probes/bench_rowwise.py), this form is 3-4
-// batches on 144.  (The step's own launches carry 8-16 workspaces, 48 MB: 33.7 -> 32.2 us, 1.5 TB/s either way.)
+// slices; a thread walks the partial rows b = slice, slice + 64, ... with 16-byte loads; the 64 slices are added in a fixed order
+// through LDS.  The reduction is a latency chain, not a bandwidth problem (a few MB per launch): what counts is how few dependent
+// memory round trips a thread makes and how many CUs take part - with 64-column tiles and 16 slices a 788-row LayerNorm workspace
+// was 12 batches deep on 36 workgroups (11.6 us for 7.3 MB; probes/bench_rowwise.py).  This form makes two trips: every partial
+// row of the thread (up to RPM_INFLIGHT at a time) and the output's float4 are loaded before the first add, then the sum goes
+// through LDS and is stored once.
+// Summation order (the bit-reproducibility contract; tests/test_reduce_partials_order_gpu.py restates it in numpy): slice sl walks
+// b = sl, sl + 64, ...; while b + 192 < nblk it adds (v[b] + v[b+64]) + (v[b+128] + v[b+192]) to its sum, then the remaining rows
+// singly; slice 0 adds the sums of slices 1..63 in order; out += total.  Rows of a width that is no multiple of 4 are added one by one.
 #define RPM_COLS 16
+// 8 rows in flight per thread: 74 VGPRs, 6 workgroups per CU (1536 in flight on the device, the step's launches are 1150-2300).  16 in flight
+// needs 130 VGPRs (3 per CU): fewer trips per workgroup but two to three rounds of workgroups, each its own chain.
+#define RPM_INFLIGHT 8
+typedef const __attribute__((address_space(1))) float* rpm_gcf;     // the descriptor's pointers name global memory: global_*, not flat_*
+typedef __attribute__((address_space(1))) float* rpm_gf;
+// Up to RPM_INFLIGHT partial rows of one slice, b0, b0 + 64, ..., all loaded before the first add.  Every load sits alone under its own
+// guard (rows past the end are not fetched; past the longest slice's end the whole wave skips the instruction), and the adds below
+// use selects, not branches: the compiler neither sinks a load behind a branch nor schedules an add (and its wait) up between loads.
+// Each group of four rows is added as one quad when its last row exists, else row by row.
+__device__ __forceinline__ void rpm_group(rpm_gcf base, size_t rs, int b0, int nblk, float4& s) {
+  float4 v[RPM_INFLIGHT];
+#pragma unroll
+  for (int j = 0; j < RPM_INFLIGHT; ++j) {
+    v[j] = float4{0.f, 0.f, 0.f, 0.f};
+    if (b0 + 64 * j < nblk) __builtin_memcpy(&v[j], base + (size_t)(b0 + 64 * j) * rs, 16);      // one 16-byte load and nothing else under the guard
+  }
+#pragma unroll
+  for (int q = 0; q < RPM_INFLIGHT; q += 4) {
+    const bool quad = b0 + 64 * (q + 3) < nblk;
+    float4 t{s.x + ((v[q].x + v[q + 1].x) + (v[q + 2].x + v[q + 3].x)), s.y + ((v[q].y + v[q + 1].y) + (v[q + 2].y + v[q + 3].y)),
+             s.z + ((v[q].z + v[q + 1].z) + (v[q + 2].z + v[q + 3].z)), s.w + ((v[q].w + v[q + 1].w) + (v[q + 2].w + v[q + 3].w))};
+    float4 u = s;
+#pragma unroll
+    for (int j = q; j < q + 3; ++j) {
+      const bool has = b0 + 64 * j < nblk;
+      u.x = has ? u.x + v[j].x : u.x; u.y = has ? u.y + v[j].y : u.y; u.z = has ? u.z + v[j].z : u.z; u.w = has ? u.w + v[j].w : u.w;
+    }
+    s.x = quad ? t.x : u.x; s.y = quad ? t.y : u.y; s.z = quad ? t.z : u.z; s.w = quad ? t.w : u.w;
+  }
+}
 __global__ __launch_bounds__(256) void reduce_partials_multi_kernel(ReduceGroup g) {
+  // the workgroup's descriptor as scalars straight from the kernel-argument segment (g is the only argument: offset 0), at a uniform
+  // index: indexing the by-value copy dynamically would put the whole array in LDS and make its pointers generic
+  const auto* gp = (const __attribute__((address_space(4))) ReduceGroup*)__builtin_amdgcn_kernarg_segment_ptr();
   int e = 0;
 #pragma unroll
-  for (int i = 1; i < RPM_MAX; ++i) if (i < g.count && (int)blockIdx.x >= g.d[i].blk0) e = i;
-  const ReduceDesc d = g.d[e];
-  const int local = blockIdx.x - d.blk0, ctiles = (d.width + RPM_COLS - 1) / RPM_COLS;
+  for (int i = 1; i < RPM_MAX; ++i) e = (i < g.count && (int)blockIdx.x >= g.d[i].blk0) ? i : e;
+  const float* part_ = gp->d[e].part;
+  float *o0 = gp->d[e].o[0], *o1 = gp->d[e].o[1], *o2 = gp->d[e].o[2], *o3 = gp->d[e].o[3];
+  const int nblk = gp->d[e].nblk, nk = gp->d[e].nk, width = gp->d[e].width, blk0 = gp->d[e].blk0;
+  const int local = blockIdx.x - blk0, ctiles = (width + RPM_COLS - 1) / RPM_COLS;
   const int k = local / ctiles, cg = threadIdx.x & 3, sl = threadIdx.x >> 2;
   const int c = (local % ctiles) * RPM_COLS + cg * 4;
   __shared__ float4 red[63][4];
   float4 s = float4{0.f, 0.f, 0.f, 0.f};
-  float* o = d.o[k];
-  const bool vec = (d.width & 3) == 0;                  // every row 16-byte aligned (the workspaces are)
-  if (o && c < d.width) {
-    const float* base = d.part + (size_t)k * d.width + c;
-    const size_t rs = (size_t)d.nk * d.width;
+  const rpm_gf o = (rpm_gf)(k == 0 ? o0 : (k == 1 ? o1 : (k == 2 ? o2 : o3)));
+  const bool vec = (width & 3) == 0;                    // every row 16-byte aligned (the workspaces are)
+  const bool live = o && c < width;
+  float4 ov = float4{0.f, 0.f, 0.f, 0.f};
+  if (live) {
+    const rpm_gcf base = (rpm_gcf)part_ + (size_t)k * width + c;
+    const size_t rs = (size_t)nk * width;
+    // the output's four floats ride with the first group of loads (an output may start at any float: four 4-byte loads, a column
+    // past the end re-reads the last one)
+    const int wl = width - 1;
+    ov = float4{o[c], o[min(c + 1, wl)], o[min(c + 2, wl)], o[min(c + 3, wl)]};
     if (vec) {
-      int b = sl;
-      for (; b + 192 < d.nblk; b += 256) {
-        const float4 v0 = *reinterpret_cast<const float4*>(base + (size_t)b * rs), v1 = *reinterpret_cast<const float4*>(base + (size_t)(b + 64) * rs),
-                     v2 = *reinterpret_cast<const float4*>(base + (size_t)(b + 128) * rs), v3 = *reinterpret_cast<const float4*>(base + (size_t)(b + 192) * rs);
-        s.x += (v0.x + v1.x) + (v2.x + v3.x); s.y += (v0.y + v1.y) + (v2.y + v3.y);
-        s.z += (v0.z + v1.z) + (v2.z + v3.z); s.w += (v0.w + v1.w) + (v2.w + v3.w);
-      }
-      for (; b < d.nblk; b += 64) {
-        const float4 v = *reinterpret_cast<const float4*>(base + (size_t)b * rs);
-        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-      }
+      // the first RPM_INFLIGHT rows per slice outside the loop (all of them up to 512 partial rows): no loop-carried wait state
+      // comes between the output's loads and these
+      rpm_group(base, rs, sl, nblk, s);
+      for (int t0 = 64 * RPM_INFLIGHT; t0 < nblk; t0 += 64 * RPM_INFLIGHT) rpm_group(base, rs, t0 + sl, nblk, s);
     } else {
-      for (int b = sl; b < d.nblk; b += 64) {
-        const float* r = base + (size_t)b * rs;
-        s.x += r[0]; if (c + 1 < d.width) s.y += r[1]; if (c + 2 < d.width) s.z += r[2]; if (c + 3 < d.width) s.w += r[3];
+      for (int b = sl; b < nblk; b += 64) {
+        const rpm_gcf r = base + (size_t)b * rs;
+        s.x += r[0]; if (c + 1 < width) s.y += r[1]; if (c + 2 < width) s.z += r[2]; if (c + 3 < width) s.w += r[3];
       }
     }
   }
   if (sl > 0) red[sl - 1][cg] = s;
   __syncthreads();
-  if (sl == 0 && o && c < d.width) {
+  if (sl == 0 && live) {
 #pragma unroll 9
     for (int i = 0; i < 63; ++i) { const float4 v = red[i][cg]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
-    o[c] += s.x;
-    if (c + 1 < d.width) o[c + 1] += s.y;
-    if (c + 2 < d.width) o[c + 2] += s.z;
-    if (c + 3 < d.width) o[c + 3] += s.w;
+    o[c] = ov.x + s.x;
+    if (c + 1 < width) o[c + 1] = ov.y + s.y;
+    if (c + 2 < width) o[c + 2] = ov.z + s.z;
+    if (c + 3 < width) o[c + 3] = ov.w + s.w;
   }
 }
 extern "C" int x2_reduce_partials_multi(const int64_t* desc, int count, void* stream) {
@@ -261,6 +299,23 @@ extern "C" int x2_reduce_partials_multi(const int64_t* desc, int count, void* st
 // A workgroup (4 waves) walks LNB_ROWS rows; each wave keeps its dw/db/dcol partials in registers, the
 // four waves are combined through LDS and written as one partial row per workgroup (ws[blk][3][D]);
 // reduce_partials_kernel then adds the partial rows into dw/db/dcol.
+//
+// The rule for a row kernel here (the backward used to break it; the next one should not):
+//   * every load a row needs - statistics, row factor, all chunks of every operand - is issued before the first instruction that
+//     consumes one.  A wave then makes one memory round trip per row, not one per chunk: at 4 waves per SIMD the number of bytes in
+//     flight, not HBM, bounds a kernel that waits after every chunk (it ran at 3-4 TB/s).
+//   * no guard around a load.  `if (c < nv) { load; use; }` makes every chunk a basic block that ends in s_waitcnt vmcnt(0).  A lane past
+//     the end of a ragged row loads the row's last float4 instead (the column is clamped, the load stays inside the row); the guard
+//     stays around the ARITHMETIC of a chunk and around its stores.  Uniform conditions (dres, the dropout masks) may branch, but only
+//     around a block of loads or a block of arithmetic, never between one chunk's load and the next chunk's.
+//   * the arithmetic keeps its basic blocks.  The backend contracts and packs fp32 operations per basic block (a product with several
+//     uses included), so merging two blocks changes which products fuse and with them the low bits: a chunk's arithmetic under a
+//     compile-time-true guard (a D == 256 * NV form) gave other bits in dx than the guarded form.  The guard is therefore a run-time one
+//     at every D, and the few additions that used to sit in a block of their own are marked `fp contract(off)`.
+//   * the wave index is made a scalar (readfirstlane): row addresses and statistics then live in SGPRs, and the accumulators plus one
+//     row of operands fit 128 VGPRs at NV = 3 (4 waves per SIMD) and 168 at NV = 4 (3 waves).
+// How to check: hipcc --offload-arch=gfx950 -O3 -S --cuda-device-only rowwise.hip, then python probes/isa_loads_waits.py rowwise.s:
+// in the row loop every global_load stands ahead of the first s_waitcnt vmcnt; -Rpass-analysis=kernel-resource-usage shows ScratchSize 0.
 #define LNB_ROWS 16
 // DYB: the incoming gradient dy is bf16 (the input-gradient GEMM of a pre-LN block writes bf16, as the reference's apex-O1
 // linears hand fp16 gradients to their LayerNorm: 2 bytes instead of 4 written by the GEMM and read here)
@@ -270,15 +325,110 @@ extern "C" int x2_reduce_partials_multi(const int64_t* desc, int count, void* st
 // MODE 0: dy fp32; 1: dy bf16; 2: dy bf16 and the by-products refer to the FINAL output times a per-row factor: the bf16 copy is
 // post_rs[row] * (dx + dres) and the third partial row its column sums - what the layer scale BELOW this LayerNorm needs of
 // its incoming gradient (x2_layerscale_finish; post_rs = DropPath factor of that branch or null).
+// The row loop of layernorm_bwd_kernel: load phase (every load of the row), compute phase, store phase.
 template <int NV, int MODE>
-__global__ __launch_bounds__(256, NV <= 3 ? 4 : 1) void layernorm_bwd_kernel(const void* __restrict__ dy_, const float* __restrict__ x,
+__device__ __forceinline__ void lnb_rows(const void* __restrict__ dy_, const float* __restrict__ x, const float* __restrict__ mean,
+                                         const float* __restrict__ rstd, const float* dres, float* dx, bf16_t* dxb, int r0, int r1, int D,
+                                         int period, const DropSpec din, const DropSpec dout, const float* __restrict__ post_rs,
+                                         const float4 (&ww)[NV], float4 (&aw)[NV], float4 (&ab)[NV], float4 (&ac)[NV]) {
+  constexpr bool DYB = MODE != 0;
+  // the wave index as a scalar: the row, its statistics and every row base address live in SGPRs, a lane keeps one 32-bit column offset
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nv = D >> 2;
+  for (int row = r0 + wv; row < r1; row += 4) {
+    const long gr = remap_row(row, period);
+    // ---- load phase: the row's statistics, its row factor and every chunk of dy, x and dres, nothing consumed yet
+    const float mu = mean[row], rs = rstd[row];
+    float f = 1.f;
+    if constexpr (MODE == 2) f = *(post_rs ? post_rs + gr : rstd + row);   // one address either way: no branch around the load
+    u32x2 dyb[NV];
+    float4 dyf[NV], xv[NV], rr[NV];
+    const size_t rowoff = (size_t)gr * D;
+    const float* xr = x + rowoff;
+    const float* rrow = dres + rowoff;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const unsigned c = lane + i * 64, cl = min(c, (unsigned)nv - 1u);
+      if constexpr (DYB) dyb[i] = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(dy_) + rowoff + cl * 4u);
+      else dyf[i] = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(dy_) + rowoff + cl * 4u);
+      xv[i] = *reinterpret_cast<const float4*>(xr + cl * 4u);
+    }
+    if (dres) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const unsigned c = lane + i * 64, cl = min(c, (unsigned)nv - 1u);
+        rr[i] = *reinterpret_cast<const float4*>(rrow + cl * 4u);
+      }
+    }
+    // ---- compute phase
+    float4 g[NV], xh[NV];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int c = lane + i * 64;
+      if (c < nv) {
+        float4 d;
+        if constexpr (DYB) d = float4{bf_lo(dyb[i].x), bf_hi(dyb[i].x), bf_lo(dyb[i].y), bf_hi(dyb[i].y)};
+        else d = dyf[i];
+        if (din.thr16) {      // the forward dropped the LN OUTPUT: mask the incoming gradient the same way
+          float dm[4];
+          drop_mul4(din, (uint32_t)gr * (uint32_t)D + (uint32_t)(c * 4), dm);
+          d.x *= dm[0]; d.y *= dm[1]; d.z *= dm[2]; d.w *= dm[3];
+        }
+        xh[i] = float4{(xv[i].x - mu) * rs, (xv[i].y - mu) * rs, (xv[i].z - mu) * rs, (xv[i].w - mu) * rs};
+        g[i] = float4{d.x * ww[i].x, d.y * ww[i].y, d.z * ww[i].z, d.w * ww[i].w};
+        s1 += g[i].x + g[i].y + g[i].z + g[i].w;
+        s2 += g[i].x * xh[i].x + g[i].y * xh[i].y + g[i].z * xh[i].z + g[i].w * xh[i].w;
+        aw[i].x += d.x * xh[i].x; aw[i].y += d.y * xh[i].y; aw[i].z += d.z * xh[i].z; aw[i].w += d.w * xh[i].w;
+        ab[i].x += d.x; ab[i].y += d.y; ab[i].z += d.z; ab[i].w += d.w;
+      }
+    }
+    const float m1 = wave_sum(s1) / D, m2 = wave_sum(s2) / D;
+    // ---- the rest of the arithmetic and the store phase (stores wait for nothing)
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int c = lane + i * 64;
+      if (c < nv) {
+        // g - m1 stays a subtraction of the rounded product g = dy * w (contracted into fma(dy, w, -m1) the low bits of dx change),
+        // then fma(-xhat, m2, .) and the product with rstd
+        float4 t;
+        {
+#pragma clang fp contract(off)
+          t = float4{g[i].x - m1, g[i].y - m1, g[i].z - m1, g[i].w - m1};
+        }
+        float4 o{rs * (t.x - xh[i].x * m2), rs * (t.y - xh[i].y * m2), rs * (t.z - xh[i].z * m2), rs * (t.w - xh[i].w * m2)};
+        // the producing linear's output was dropped before the residual add: its gradient (bf16 copy, bias sums)
+        // carries that mask, the residual branch (dx) does not
+        float4 om = o;
+        if (dout.thr16) {
+          float dm[4];
+          drop_mul4(dout, (uint32_t)gr * (uint32_t)D + (uint32_t)(c * 4), dm);
+          om.x *= dm[0]; om.y *= dm[1]; om.z *= dm[2]; om.w *= dm[3];
+        }
+        if (dres) {
+#pragma clang fp contract(off)
+          o.x += rr[i].x; o.y += rr[i].y; o.z += rr[i].z; o.w += rr[i].w;       // plain adds here and below: never rstd * (.) fused into them
+        }
+        if (dx) *reinterpret_cast<float4*>(dx + rowoff + c * 4) = o;
+        if constexpr (MODE == 2) { om = o; if (post_rs) { om.x *= f; om.y *= f; om.z *= f; om.w *= f; } }
+        {
+#pragma clang fp contract(off)
+          ac[i].x += om.x; ac[i].y += om.y; ac[i].z += om.z; ac[i].w += om.w;
+        }
+        if (dxb) *reinterpret_cast<u32x2*>(dxb + rowoff + c * 4) = u32x2{pack_bf16(om.x, om.y), pack_bf16(om.z, om.w)};
+      }
+    }
+  }
+}
+
+template <int NV, int MODE>
+__global__ __launch_bounds__(256, NV <= 3 ? 4 : (NV == 4 ? 3 : 1)) void layernorm_bwd_kernel(const void* __restrict__ dy_, const float* __restrict__ x,
                                                             const float* __restrict__ mean, const float* __restrict__ rstd,
                                                             const float* __restrict__ w, const float* dres, float* dx, bf16_t* dxb,
                                                             float* ws, int rows, int D, int period,
                                                             DropSpec din_, DropSpec dout_, const uint32_t* __restrict__ epoch,
                                                             const float* __restrict__ post_rs) {
   constexpr int NSET = 3;
-  constexpr bool DYB = MODE != 0;
   extern __shared__ __attribute__((aligned(16))) float red[];      // [NSET][3 waves][D]
   const DropSpec din = drop_at_epoch(din_, epoch), dout = drop_at_epoch(dout_, epoch);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -291,59 +441,8 @@ __global__ __launch_bounds__(256, NV <= 3 ? 4 : 1) void layernorm_bwd_kernel(con
     aw[i] = float4{0.f, 0.f, 0.f, 0.f}; ab[i] = float4{0.f, 0.f, 0.f, 0.f}; ac[i] = float4{0.f, 0.f, 0.f, 0.f};
   }
   const int r0 = blockIdx.x * LNB_ROWS, r1 = min(rows, r0 + LNB_ROWS);
-  for (int row = r0 + wv; row < r1; row += 4) {
-    const long gr = remap_row(row, period);
-    const float mu = mean[row], rs = rstd[row];
-    float4 g[NV], xh[NV];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = lane + i * 64;
-      if (c < nv) {
-        float4 d;
-        if constexpr (DYB) {
-          const u32x2 raw = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(dy_) + gr * D + c * 4);
-          d = float4{bf_lo(raw.x), bf_hi(raw.x), bf_lo(raw.y), bf_hi(raw.y)};
-        } else {
-          d = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(dy_) + gr * D + c * 4);
-        }
-        const float4 xv = *reinterpret_cast<const float4*>(x + gr * D + c * 4);
-        if (din.thr16) {      // the forward dropped the LN OUTPUT: mask the incoming gradient the same way
-          float dm[4];
-          drop_mul4(din, (uint32_t)gr * (uint32_t)D + (uint32_t)(c * 4), dm);
-          d.x *= dm[0]; d.y *= dm[1]; d.z *= dm[2]; d.w *= dm[3];
-        }
-        xh[i] = float4{(xv.x - mu) * rs, (xv.y - mu) * rs, (xv.z - mu) * rs, (xv.w - mu) * rs};
-        g[i] = float4{d.x * ww[i].x, d.y * ww[i].y, d.z * ww[i].z, d.w * ww[i].w};
-        s1 += g[i].x + g[i].y + g[i].z + g[i].w;
-        s2 += g[i].x * xh[i].x + g[i].y * xh[i].y + g[i].z * xh[i].z + g[i].w * xh[i].w;
-        aw[i].x += d.x * xh[i].x; aw[i].y += d.y * xh[i].y; aw[i].z += d.z * xh[i].z; aw[i].w += d.w * xh[i].w;
-        ab[i].x += d.x; ab[i].y += d.y; ab[i].z += d.z; ab[i].w += d.w;
-      }
-    }
-    const float m1 = wave_sum(s1) / D, m2 = wave_sum(s2) / D;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = lane + i * 64;
-      if (c < nv) {
-        float4 o{rs * (g[i].x - m1 - xh[i].x * m2), rs * (g[i].y - m1 - xh[i].y * m2), rs * (g[i].z - m1 - xh[i].z * m2), rs * (g[i].w - m1 - xh[i].w * m2)};
-        // the producing linear's output was dropped before the residual add: its gradient (bf16 copy, bias sums)
-        // carries that mask, the residual branch (dx) does not
-        float4 om = o;
-        if (dout.thr16) {
-          float dm[4];
-          drop_mul4(dout, (uint32_t)gr * (uint32_t)D + (uint32_t)(c * 4), dm);
-          om.x *= dm[0]; om.y *= dm[1]; om.z *= dm[2]; om.w *= dm[3];
-        }
-        if (dres) { const float4 rr = *reinterpret_cast<const float4*>(dres + gr * D + c * 4); o.x += rr.x; o.y += rr.y; o.z += rr.z; o.w += rr.w; }
-        if (dx) *reinterpret_cast<float4*>(dx + gr * D + c * 4) = o;
-        if constexpr (MODE == 2) { om = o; if (post_rs) { const float f = post_rs[gr]; om.x *= f; om.y *= f; om.z *= f; om.w *= f; } }
-        ac[i].x += om.x; ac[i].y += om.y; ac[i].z += om.z; ac[i].w += om.w;
-        if (dxb) *reinterpret_cast<u32x2*>(dxb + gr * D + c * 4) = u32x2{pack_bf16(om.x, om.y), pack_bf16(om.z, om.w)};
-      }
-    }
-  }
-  // combine the 4 waves: waves 1..3 park their partials in LDS, wave 0 adds them and issues the atomics
+  lnb_rows<NV, MODE>(dy_, x, mean, rstd, dres, dx, dxb, r0, r1, D, period, din, dout, post_rs, ww, aw, ab, ac);
+  // combine the 4 waves: waves 1..3 park their partials in LDS, wave 0 adds them and writes the workgroup's partial row
   if (wv > 0) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
