@@ -84,6 +84,23 @@ int x2_gemm_nt_splitk(const void* A, const void* B, float* C, int M, int N, int 
  * count.  Otherwise 128x128 tiles, where split > 1 (without a workspace) adds with fp32 atomics and requires accumulate. */
 int x2_gemm_tn_grouped(const int64_t* problems, int count, int accumulate, int split, float* ws, long ws_floats,
                        void* stream);
+/* A queue of such problems (every layer whose operands are ready) as whole rounds of the compute units: additive to ABI v14, no existing
+ * signature changes.  The 256x256 tiles of all problems are walked in the order given.  The largest multiple of `cus` tiles (main part) runs
+ * unsplit and stores directly, cut into launches only where a launch's 32 windows run out (then at the last whole round they reach); a window is (problem, first tile, tile count) of a
+ * problem's own tile grid, so a launch may end or begin in the middle of a problem.  The tiles left over (fewer than cus) are one more launch
+ * under the split rule of x2_gemm_tn_grouped (fullest last round, slices of at least 16 contraction steps, workspace permitting): partial
+ * tiles and the fixed-order reduction apply to those tiles only.  A queue of at most one round is all remainder: x2_gemm_tn_grouped(split = 0).
+ *   x2_tn_plan : the plan, pure host arithmetic (no device call).  shapes: count rows of 3 int64 {Mc, N, K}; cus <= 0: the count the library
+ *       plans with (the device's, less x2_tune(12)); ws_floats: room for partial tiles.  windows: rows of 4 int32 {launch, problem, first tile,
+ *       tile count} in launch order; launches: rows of 2 int32 {split, 1 = remainder}.  *n_windows / *n_launches: the plan's sizes; with
+ *       max_windows == max_launches == 0 only they are written, more rows than the room given returns -1.
+ *   x2_gemm_tn_queue : runs launches [first_launch, first_launch + n_launches) of that plan (n_launches == 0: all from first_launch on) for
+ *       problems as x2_gemm_tn_grouped takes them, any count.  Work that must follow the launch completing a problem runs the plan a launch
+ *       at a time.  Fewer than 24 tiles in all: x2_gemm_tn_grouped in groups of 8 (one launch, first_launch must be 0). */
+int x2_tn_plan(const int64_t* shapes, int count, int cus, long ws_floats, int* windows, int max_windows, int* launches, int max_launches,
+               int* n_windows, int* n_launches);
+int x2_gemm_tn_queue(const int64_t* problems, int count, int accumulate, float* ws, long ws_floats, int first_launch, int n_launches,
+                     void* stream);
 
 /* ---- fused attention, head dim 64 (csrc/attention.hip) ----------------------------------------------
  * beit2.py:135-159 (q*scale, QK^T, + relative_position_bias, softmax, PV); xbert.py:364-409 (QK^T/sqrt(d),

@@ -36,6 +36,7 @@ _SIGS = {
     "x2_gemm_nt_splitk": [P, P, P, I, I, I, I, I, I, I, P, L, P],
     "x2_gemm_nt_dgelu_colparts": [P, P, P, I, I, I, I, I, I, P, I, P, C.POINTER(I), P],
     "x2_gemm_tn_grouped": [P, I, I, I, P, L, P],
+    "x2_gemm_tn_queue": [P, I, I, P, L, I, I, P],
     "x2_attn_fwd": [C.POINTER(AttnArgs), P],
     "x2_attn_bwd": [C.POINTER(AttnArgs), P],
     "x2_layernorm_fwd": [P, P, P, P, P, P, P, I, I, F, I, U, U, F, P, P],
@@ -122,7 +123,7 @@ _COMM_SIGS = {
     "x2_comm_destroy": [P],
 }
 EXPORTS = sorted(list(_SIGS) + list(_COMM_SIGS) + ["x2_last_error", "x2_abi_version", "x2_device_cus", "x2_tune", "x2_tune_get",
-                                                         "x2_attn_bwd_one_pass"])
+                                                         "x2_attn_bwd_one_pass", "x2_tn_plan"])
 
 _lib = None
 
@@ -151,6 +152,7 @@ def lib():
         h.x2_tune.argtypes, h.x2_tune.restype = [I, I], I
         h.x2_tune_get.argtypes, h.x2_tune_get.restype = [I], I
         h.x2_attn_bwd_one_pass.argtypes, h.x2_attn_bwd_one_pass.restype = [C.POINTER(AttnArgs)], I
+        h.x2_tn_plan.argtypes, h.x2_tn_plan.restype = [P, I, I, L, P, I, P, I, C.POINTER(I), C.POINTER(I)], I     # host only: no stream
         for kv in filter(None, os.environ.get("X2_TUNE", "").split(",")):      # probes: "key=value,..." kernel-variant knobs (csrc/gemm.hip)
             k, v = kv.split("=")
             set_tune(int(k), int(v), h)

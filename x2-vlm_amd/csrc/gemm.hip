@@ -13,7 +13,9 @@
 // Replaces (reference, all implicit ATen/cuBLAS calls): F.linear in beit2.py:131,160,62,66 and
 // xbert.py:338-350,428,497,512,798,822 and their autograd backward.
 #include "x2_common.h"
+#include <algorithm>
 #include <type_traits>
+#include <vector>
 
 #define BM 128
 #define BN 128
@@ -1479,9 +1481,11 @@ struct TNProblem {
   int Mc, N, K;           // contraction length, output rows, output cols
   int lda, ldb, ldc;
   int n_ld, k_ld;         // readable columns of A / B rows (>= N / K, multiple of 8)
-  int tile_begin, tiles_k;
+  int tile_begin, tiles_k; // first position of this entry inside the launch; K tiles of the problem's own grid
+  int tile_first;         // the entry is a WINDOW of the problem's grid: launch position tile_begin is tile tile_first of the problem
 };
-struct GemmTNGroup { TNProblem p[8]; int count; int accumulate; };
+#define TN_MAX_ENTRIES 32   // 32 x 72 bytes by value: 2.3 KB of the 4 KB kernel-argument segment
+struct GemmTNGroup { TNProblem p[TN_MAX_ENTRIES]; int count; int accumulate; };
 
 __device__ __forceinline__ int tn_f(int r) { return (r & 3) | (((r >> 3) & 1) << 2); }
 
@@ -1493,9 +1497,9 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmTNGroup g) {
   int t = xcd_remap(blockIdx.x, gridDim.x);
   int pi = 0;
 #pragma unroll
-  for (int i = 1; i < 8; ++i) if (i < g.count && t >= g.p[i].tile_begin) pi = i;
+  for (int i = 1; i < TN_MAX_ENTRIES; ++i) if (i < g.count && t >= g.p[i].tile_begin) pi = i;
   const TNProblem p = g.p[pi];
-  t -= p.tile_begin;
+  t -= p.tile_begin - p.tile_first;
   int tnn, tkk;
   tile_coords(t, (p.N + 127) / 128, p.tiles_k, 8, tnn, tkk);
   const int n0 = tnn * 128, k0 = tkk * 128;
@@ -1637,10 +1641,10 @@ __global__ __launch_bounds__(512) void gemm_tn256_kernel(GemmTNGroup g, float* w
   const int tile = xcd_remap(blockIdx.x, gridDim.x);
   int pi = 0;
 #pragma unroll
-  for (int i = 1; i < 8; ++i) if (i < g.count && tile >= g.p[i].tile_begin) pi = i;
+  for (int i = 1; i < TN_MAX_ENTRIES; ++i) if (i < g.count && tile >= g.p[i].tile_begin) pi = i;
   const TNProblem p = g.p[pi];
   int tnn, tkk;
-  tile_coords(tile - p.tile_begin, (p.N + 255) / 256, p.tiles_k, 4, tnn, tkk);
+  tile_coords(tile - p.tile_begin + p.tile_first, (p.N + 255) / 256, p.tiles_k, 4, tnn, tkk);
   const int n0 = tnn * 256, k0 = tkk * 256;
   const int steps = (p.Mc + BK - 1) / BK, rag = p.Mc % BK;        // host guarantees steps >= gridDim.y; rag = rows of a partial last step
   const int s_begin = (int)((long)steps * blockIdx.y / gridDim.y), s_end = (int)((long)steps * (blockIdx.y + 1) / gridDim.y);
@@ -1784,10 +1788,10 @@ __global__ __launch_bounds__(256) void gemm_tn256_reduce_kernel(GemmTNGroup g, c
   const int tile = blockIdx.x >> 6;
   int pi = 0;
 #pragma unroll
-  for (int i = 1; i < 8; ++i) if (i < g.count && tile >= g.p[i].tile_begin) pi = i;
+  for (int i = 1; i < TN_MAX_ENTRIES; ++i) if (i < g.count && tile >= g.p[i].tile_begin) pi = i;
   const TNProblem p = g.p[pi];
   int tnn, tkk;
-  tile_coords(tile - p.tile_begin, (p.N + 255) / 256, p.tiles_k, 4, tnn, tkk);
+  tile_coords(tile - p.tile_begin + p.tile_first, (p.N + 255) / 256, p.tiles_k, 4, tnn, tkk);
   const int e = (blockIdx.x & 63) * 256 + threadIdx.x;             // float4 index inside the tile
   const int lane = e & 63, ij = (e >> 6) & 31, wave = e >> 11;
   const int i = ij >> 3, j = ij & 7, fi = lane & 15, fg = lane >> 4, wr = wave >> 2, wc = wave & 3;
@@ -1804,6 +1808,49 @@ __global__ __launch_bounds__(256) void gemm_tn256_reduce_kernel(GemmTNGroup g, c
   *reinterpret_cast<float4*>(dst) = o;
 }
 
+// one row of 11 int64 {A, B, C, Mc, N, K, lda, ldb, ldc, n_ld, k_ld} -> descriptor entry (a whole problem: tile_first = 0)
+static int tn_parse(const char* who, const int64_t* q, int i, TNProblem& p) {
+  p.A = (const bf16_t*)q[0]; p.B = (const bf16_t*)q[1]; p.C = (float*)q[2];
+  p.Mc = (int)q[3]; p.N = (int)q[4]; p.K = (int)q[5]; p.lda = (int)q[6]; p.ldb = (int)q[7]; p.ldc = (int)q[8];
+  p.n_ld = (int)q[9]; p.k_ld = (int)q[10];
+  p.tile_begin = 0; p.tiles_k = 0; p.tile_first = 0;
+  X2_REQUIRE(p.Mc > 0 && p.N > 0 && p.K > 0, "%s[%d]: empty problem", who, i);
+  X2_REQUIRE(p.K % 4 == 0 && p.ldc % 4 == 0, "%s[%d]: K, ldc must be multiples of 4", who, i);
+  X2_REQUIRE(p.lda % 8 == 0 && p.ldb % 8 == 0 && p.n_ld % 8 == 0 && p.k_ld % 8 == 0 && p.n_ld >= 8 && p.k_ld >= 8,
+             "%s[%d]: rows must be 16-byte granular", who, i);
+  X2_REQUIRE(p.n_ld <= p.lda && p.k_ld <= p.ldb, "%s[%d]: n_ld/k_ld exceed leading dims", who, i);
+  return X2_OK;
+}
+// slices of the contraction for a launch of t tiles of 256x256 on `cus` one-workgroup-per-CU slots: fullest last round, fewest partial
+// tiles on a tie, no slice shorter than 16 steps; then what the workspace allows
+static int tn_split_rule(int t, int min_steps, int cus, int split, bool have_ws, long ws_floats) {
+  int sp = split;
+  if (sp == 0) {
+    double best = -1.0; sp = 1;
+    for (int c = 1; c <= 4 && min_steps / c >= 16; ++c) {     // a slice shorter than 16 steps costs more in partial tiles than it fills
+      const long blocks = (long)t * c;
+      const double fill = (double)blocks / (double)(((blocks + cus - 1) / cus) * cus);
+      if (fill > best + 0.03) { best = fill; sp = c; }
+    }
+  }
+  while (sp > 1 && (sp > min_steps || !have_ws || (long)sp * t * 65536 > ws_floats)) --sp;
+  return sp;
+}
+// g.p[0 .. count) with tile_begin / tiles_k / tile_first set, t tiles in all, sp slices: the 256x256 kernel (+ the fixed-order reducer)
+static void tn256_launch(const GemmTNGroup& g, int t, int sp, float* ws, hipStream_t stream) {
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn256_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, T2_LDS_BYTES);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn256_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, T2_LDS_BYTES);
+    attr = true;
+  }
+  bool ragged = false;
+  for (int i = 0; i < g.count; ++i) ragged = ragged || (g.p[i].Mc % BK != 0);
+  if (ragged) hipLaunchKernelGGL(gemm_tn256_kernel<true>, dim3(t, sp), dim3(512), T2_LDS_BYTES, stream, g, ws, t);
+  else hipLaunchKernelGGL(gemm_tn256_kernel<false>, dim3(t, sp), dim3(512), T2_LDS_BYTES, stream, g, ws, t);
+  if (sp > 1) hipLaunchKernelGGL(gemm_tn256_reduce_kernel, dim3(t * 64), dim3(256), 0, stream, g, ws, t, sp);
+}
+
 // problems: `count` rows of 11 int64: {A, B, C, Mc, N, K, lda, ldb, ldc, n_ld, k_ld}.
 // split = 0: automatic.  ws / ws_floats: scratch for the split partial tiles of the 256x256 kernel (may be null: then
 // it never splits).  The 256x256 kernel (any contraction length: a partial last step reads zeros) is used from 24 tiles
@@ -1812,21 +1859,12 @@ extern "C" int x2_gemm_tn_grouped(const int64_t* problems, int count, int accumu
                                   void* stream) {
   X2_REQUIRE(count >= 1 && count <= 8, "x2_gemm_tn_grouped: count=%d not in [1,8]", count);
   X2_REQUIRE(split >= 0, "x2_gemm_tn_grouped: split=%d", split);
-  GemmTNGroup g; g.count = count; g.accumulate = accumulate;
-  int tiles = 0, tiles256 = 0, min_steps = 1 << 30;
+  GemmTNGroup g{}; g.count = count; g.accumulate = accumulate;          // unused entries: zeros
+  int tiles256 = 0, min_steps = 1 << 30;
   bool big = g_tune[5] != 1;
   for (int i = 0; i < count; ++i) {
-    const int64_t* q = problems + i * 11;
     TNProblem& p = g.p[i];
-    p.A = (const bf16_t*)q[0]; p.B = (const bf16_t*)q[1]; p.C = (float*)q[2];
-    p.Mc = (int)q[3]; p.N = (int)q[4]; p.K = (int)q[5]; p.lda = (int)q[6]; p.ldb = (int)q[7]; p.ldc = (int)q[8];
-    p.n_ld = (int)q[9]; p.k_ld = (int)q[10];
-    X2_REQUIRE(p.Mc > 0 && p.N > 0 && p.K > 0, "x2_gemm_tn_grouped[%d]: empty problem", i);
-    X2_REQUIRE(p.K % 4 == 0 && p.ldc % 4 == 0, "x2_gemm_tn_grouped[%d]: K, ldc must be multiples of 4", i);
-    X2_REQUIRE(p.lda % 8 == 0 && p.ldb % 8 == 0 && p.n_ld % 8 == 0 && p.k_ld % 8 == 0 && p.n_ld >= 8 && p.k_ld >= 8,
-               "x2_gemm_tn_grouped[%d]: rows must be 16-byte granular", i);
-    X2_REQUIRE(p.n_ld <= p.lda && p.k_ld <= p.ldb, "x2_gemm_tn_grouped[%d]: n_ld/k_ld exceed leading dims", i);
-    tiles += ((p.N + 127) / 128) * ((p.K + 127) / 128);
+    if (int rc = tn_parse("x2_gemm_tn_grouped", problems + i * 11, i, p)) return rc;
     tiles256 += ((p.N + 255) / 256) * ((p.K + 255) / 256);
     const int steps_i = (p.Mc + BK - 1) / BK;
     min_steps = steps_i < min_steps ? steps_i : min_steps;
@@ -1838,28 +1876,8 @@ extern "C" int x2_gemm_tn_grouped(const int64_t* problems, int count, int accumu
   if (big) {
     int t = 0;
     for (int i = 0; i < count; ++i) { g.p[i].tile_begin = t; g.p[i].tiles_k = (g.p[i].K + 255) / 256; t += ((g.p[i].N + 255) / 256) * g.p[i].tiles_k; }
-    const int cus = x2_cus();
-    int sp = split;
-    if (sp == 0) {              // fullest last round of one-workgroup-per-CU slots, fewest partial tiles on a tie
-      double best = -1.0; sp = 1;
-      for (int c = 1; c <= 4 && min_steps / c >= 16; ++c) {     // a slice shorter than 16 steps costs more in partial tiles than it fills
-        const long blocks = (long)t * c;
-        const double fill = (double)blocks / (double)(((blocks + cus - 1) / cus) * cus);
-        if (fill > best + 0.03) { best = fill; sp = c; }
-      }
-    }
-    while (sp > 1 && (sp > min_steps || !ws || (long)sp * t * 65536 > ws_floats)) --sp;
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn256_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, T2_LDS_BYTES);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn256_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, T2_LDS_BYTES);
-      attr = true;
-    }
-    bool ragged = false;
-    for (int i = 0; i < count; ++i) ragged = ragged || (g.p[i].Mc % BK != 0);
-    if (ragged) hipLaunchKernelGGL(gemm_tn256_kernel<true>, dim3(t, sp), dim3(512), T2_LDS_BYTES, (hipStream_t)stream, g, ws, t);
-    else hipLaunchKernelGGL(gemm_tn256_kernel<false>, dim3(t, sp), dim3(512), T2_LDS_BYTES, (hipStream_t)stream, g, ws, t);
-    if (sp > 1) hipLaunchKernelGGL(gemm_tn256_reduce_kernel, dim3(t * 64), dim3(256), 0, (hipStream_t)stream, g, ws, t, sp);
+    const int sp = tn_split_rule(t, min_steps, x2_cus(), split, ws != nullptr, ws_floats);
+    tn256_launch(g, t, sp, ws, (hipStream_t)stream);
     return x2_check_launch("x2_gemm_tn_grouped");
   }
   if (split == 0) split = 1;
@@ -1868,4 +1886,125 @@ extern "C" int x2_gemm_tn_grouped(const int64_t* problems, int count, int accumu
   for (int i = 0; i < count; ++i) { g.p[i].tile_begin = t; g.p[i].tiles_k = (g.p[i].K + 127) / 128; t += ((g.p[i].N + 127) / 128) * g.p[i].tiles_k; }
   hipLaunchKernelGGL(gemm_tn_kernel, dim3(t, split), dim3(256), GEMM_LDS_BYTES, (hipStream_t)stream, g);
   return x2_check_launch("x2_gemm_tn_grouped");
+}
+
+// ---------------------------------------------------------------------------------------------
+// A QUEUE of weight-gradient problems (all layers whose operands are ready) as whole rounds of the CUs.  The launch unit of
+// x2_gemm_tn_grouped is a layer: 216 tiles (a pair of vision blocks) or 144 tiles x split 3 (a fusion layer) on 256 CUs leave
+// a sixth of the chip idle for a whole contraction, or pay 113 MB of partial tiles per layer.  Here the tiles of every
+// queued problem are walked in the given order:
+//   main       the largest multiple of `cus` tiles: unsplit, stored directly, cut into launches only where a launch's 32
+//              descriptor entries run out (then at the last whole round they reach).  A launch entry is a WINDOW (problem, first tile, tile count) of a problem's grid.
+//   remainder  the tiles left (fewer than cus): one more launch under the split rule of x2_gemm_tn_grouped; partial tiles and
+//              the fixed-order reducer apply to these tiles only.
+// A queue of at most one round is its own remainder: it behaves as x2_gemm_tn_grouped(split = 0).
+// The plan is pure host arithmetic (x2_tn_plan: no device call), so it is tested without a GPU.
+// ---------------------------------------------------------------------------------------------
+struct TNWindow { int launch, problem, first, tiles; };
+struct TNPlan { std::vector<TNWindow> win; std::vector<int> split, remainder; };   // per launch: slices; 1 = part of the remainder
+static void tn_plan(const int64_t* shapes, int stride, int count, int cus, long ws_floats, TNPlan& plan) {
+  std::vector<int> tiles(count), steps(count);
+  long total = 0;
+  for (int i = 0; i < count; ++i) {
+    const int64_t* q = shapes + (size_t)i * stride;
+    tiles[i] = (int)(((q[1] + 255) / 256) * ((q[2] + 255) / 256));
+    steps[i] = (int)((q[0] + BK - 1) / BK);
+    total += tiles[i];
+  }
+  const long main_tiles = total / cus * cus;
+  // windows of the tile range [from, to) of the queue, at most TN_MAX_ENTRIES of them: appended as one launch, returns where it stopped
+  int launch = -1;
+  auto emit = [&](long from, long to, bool rem, bool dry) -> long {
+    if (!dry) { ++launch; plan.split.push_back(1); plan.remainder.push_back(rem ? 1 : 0); }
+    long begin = 0, pos = from;
+    int entries = 0;
+    for (int i = 0; i < count && pos < to && entries < TN_MAX_ENTRIES; begin += tiles[i], ++i) {
+      if (pos >= begin + tiles[i]) continue;
+      const int first = (int)(pos - begin), n = (int)std::min<long>(tiles[i] - first, to - pos);
+      if (!dry) plan.win.push_back(TNWindow{launch, i, first, n});
+      ++entries; pos += n;
+    }
+    return pos;
+  };
+  for (long pos = 0; pos < main_tiles;) {
+    // where the 32 entries run out before the main part does, the launch ends at the last whole round it reaches: a launch that
+    // ends inside a round leaves compute units idle until the next launch may start
+    long end = emit(pos, main_tiles, false, true);
+    if (end < main_tiles && end / cus * cus > pos) end = end / cus * cus;
+    pos = emit(pos, end, false, false);
+  }
+  for (long pos = main_tiles; pos < total;) pos = emit(pos, total, true, false);
+  for (int l = 0; l <= launch; ++l) {
+    if (!plan.remainder[l]) continue;
+    int t = 0, min_steps = 1 << 30;
+    for (const TNWindow& w : plan.win) if (w.launch == l) { t += w.tiles; min_steps = std::min(min_steps, steps[w.problem]); }
+    plan.split[l] = tn_split_rule(t, min_steps, cus, 0, ws_floats > 0, ws_floats);
+  }
+}
+
+// shapes: count rows of 3 int64 {Mc, N, K}; cus: one-workgroup-per-CU slots (<= 0: what the library uses, x2_tune(12) included);
+// ws_floats: size of the partial-tile workspace the remainder may use.  windows: up to max_windows rows of 4 int32
+// {launch, problem, first tile, tile count} in launch order; launches: up to max_launches rows of 2 int32 {split, 1 if remainder}.
+// n_windows / n_launches receive the plan's sizes (also when they exceed the room given: -1 then, nothing half-written is valid).
+extern "C" int x2_tn_plan(const int64_t* shapes, int count, int cus, long ws_floats, int* windows, int max_windows, int* launches,
+                          int max_launches, int* n_windows, int* n_launches) {
+  X2_REQUIRE(shapes && count >= 1 && n_windows && n_launches, "x2_tn_plan: null argument or count=%d", count);
+  for (int i = 0; i < count; ++i)
+    X2_REQUIRE(shapes[3 * i] > 0 && shapes[3 * i + 1] > 0 && shapes[3 * i + 2] > 0 && shapes[3 * i] < (1L << 31) && shapes[3 * i + 1] < (1L << 24) &&
+               shapes[3 * i + 2] < (1L << 24), "x2_tn_plan[%d]: Mc, N, K out of range", i);
+  if (cus <= 0) cus = x2_cus();
+  TNPlan plan;
+  tn_plan(shapes, 3, count, cus, ws_floats, plan);
+  *n_windows = (int)plan.win.size(); *n_launches = (int)plan.split.size();
+  X2_REQUIRE((windows || max_windows == 0) && (launches || max_launches == 0), "x2_tn_plan: null output");
+  if (max_windows == 0 && max_launches == 0) return X2_OK;           // a size query
+  X2_REQUIRE(*n_windows <= max_windows && *n_launches <= max_launches, "x2_tn_plan: %d windows, %d launches exceed the room given (%d, %d)",
+             *n_windows, *n_launches, max_windows, max_launches);
+  for (size_t w = 0; w < plan.win.size(); ++w) {
+    windows[4 * w] = plan.win[w].launch; windows[4 * w + 1] = plan.win[w].problem; windows[4 * w + 2] = plan.win[w].first; windows[4 * w + 3] = plan.win[w].tiles;
+  }
+  for (size_t l = 0; l < plan.split.size(); ++l) { launches[2 * l] = plan.split[l]; launches[2 * l + 1] = plan.remainder[l]; }
+  return X2_OK;
+}
+
+// Runs launches [first_launch, first_launch + n_launches) of the plan of `problems` (rows as x2_gemm_tn_grouped; n_launches = 0: all
+// of them from first_launch on).  A caller with work that must follow the launch completing a problem (x2_tn_plan tells which) runs the
+// plan a launch at a time; the plan is the same on every call with the same problems, CU reservation and workspace size.
+// A queue that is a single round of fewer than 24 tiles goes through x2_gemm_tn_grouped (split = 0) in groups of 8: the 128x128 kernel.
+extern "C" int x2_gemm_tn_queue(const int64_t* problems, int count, int accumulate, float* ws, long ws_floats, int first_launch,
+                                int n_launches, void* stream) {
+  X2_REQUIRE(problems && count >= 1 && first_launch >= 0 && n_launches >= 0, "x2_gemm_tn_queue: count=%d first_launch=%d n_launches=%d", count,
+             first_launch, n_launches);
+  std::vector<TNProblem> pr(count);
+  long tiles256 = 0;
+  for (int i = 0; i < count; ++i) {
+    if (int rc = tn_parse("x2_gemm_tn_queue", problems + (size_t)i * 11, i, pr[i])) return rc;
+    tiles256 += (long)((pr[i].N + 255) / 256) * ((pr[i].K + 255) / 256);
+  }
+  if (g_tune[5] == 1 || (g_tune[5] != 2 && tiles256 < 24)) {
+    X2_REQUIRE(first_launch == 0, "x2_gemm_tn_queue: first_launch=%d of a one-launch plan", first_launch);
+    for (int i = 0; i < count; i += 8)
+      if (int rc = x2_gemm_tn_grouped(problems + (size_t)i * 11, std::min(8, count - i), accumulate, 0, ws, ws_floats, stream)) return rc;
+    return X2_OK;
+  }
+  if (!ws) ws_floats = 0;
+  TNPlan plan;
+  tn_plan(problems + 3, 11, count, x2_cus(), ws_floats, plan);
+  const int nl = (int)plan.split.size();
+  X2_REQUIRE(first_launch < nl, "x2_gemm_tn_queue: first_launch=%d of %d launches", first_launch, nl);
+  const int end = n_launches == 0 ? nl : std::min(nl, first_launch + n_launches);
+  size_t w = 0;
+  for (int l = 0; l < end; ++l) {
+    GemmTNGroup g{}; g.count = 0; g.accumulate = accumulate;            // unused entries: zeros
+    int t = 0;
+    for (; w < plan.win.size() && plan.win[w].launch == l; ++w) {
+      TNProblem& p = g.p[g.count++];
+      p = pr[plan.win[w].problem];
+      p.tile_begin = t; p.tiles_k = (p.K + 255) / 256; p.tile_first = plan.win[w].first;
+      t += plan.win[w].tiles;
+    }
+    if (l < first_launch) continue;
+    tn256_launch(g, t, plan.split[l], ws, (hipStream_t)stream);
+  }
+  return x2_check_launch("x2_gemm_tn_queue");
 }

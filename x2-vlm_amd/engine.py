@@ -353,7 +353,9 @@ def _begin_layer_backward():
 class _LayerPairs:
     """Weight gradients of TWO consecutive layers per grouped launch when they fit its 8 problem slots (a vision block
     or a text layer has 4): 216 tiles of 256x256 fill the 256 CUs without splitting the contraction, so there are no
-    partial tiles to write and re-add, and half the launches.  Layers with more problems (fusion: 7) go alone.
+    partial tiles to write and re-add, and half the launches.  Layers with more problems (fusion: 7) go alone - in line; where
+    WGRAD_QUEUE collects them (graph.SegmentedStep's tail segment) all of them run as ONE queue planned across layers
+    (run_wgrad_queue below: whole rounds of the compute units unsplit, one split remainder).
     (Measured and dropped: un-pairing the LAST two vision layers so that only two weight gradients remain after the critical
     stream has finished block 0 - the split launches cost more than the shorter tail saves: 25.48 -> 25.90 ms per base step.)"""
 
@@ -409,17 +411,25 @@ class _LayerPairs:
 
             extra = list(extra)
 
-            def later():
+            def pre():
                 for fn in extra:
                     fn()
                 if def_a:
                     K.reduce_partials_multi(def_a)
-                K.gemm_tn_grouped(tn_a)
+
+            def post():
                 if fin_a:
                     K.layerscale_finish(fin_a)
                 if GRAD_READY_HOOK is not None:
                     for flat, key, params in pubs:
                         GRAD_READY_HOOK(flat, key, None, params)
+
+            def later():
+                pre()
+                K.gemm_tn_grouped(tn_a)
+                post()
+            # the three parts, for run_wgrad_queue: the GEMMs of several layers' closures are planned as one queue
+            later.pre, later.tn, later.post = pre, tn_a, post
             # one contribution per parameter: autograd ADDS a second call's arena view to the first's the moment it receives
             # it - both still empty - and the late GEMMs would then overwrite the sum with one of them
             later.params = set(id(p_) for _, _, ps in pubs for p_ in ps)
@@ -434,6 +444,29 @@ class _LayerPairs:
         done = SIDE.launch(work, keep)
         for G, _, _ in entries:
             G.publish(done)
+
+
+def run_wgrad_queue(work):
+    """Run the closures WGRAD_QUEUE collected (one per layer or layer pair) with their GEMMs planned ACROSS layers: every layer's
+    stage-2 reductions first, then the weight-gradient GEMMs of all layers as one K.gemm_tn_queue - whole rounds of the compute units
+    unsplit, split partial tiles only for the tiles left over (six fusion layers: 864 tiles = 3 rounds + 96, instead of six launches of
+    144 tiles x split 3 with 113 MB of partial tiles each) - in the layers' order and, inside a layer, in the order the layer gave
+    (longest contraction first).  A layer's layerscale_finish and GRAD_READY_HOOK run right behind the launch that holds the last tile
+    of its last problem, never before it: the hook's consumer (DDP) all-reduces that arena.  A single closure is its own plan."""
+    work = list(work or ())
+    if len(work) < 2:
+        for fn in work:
+            fn()
+        return
+    for fn in work:
+        assert fn.tn, "engine.run_wgrad_queue: a queued layer without weight-gradient problems"
+        fn.pre()
+    tn, ends = [], {}
+    for fn in work:
+        tn += fn.tn
+        ends[len(tn) - 1] = fn.post          # fn.tn is not empty: one key per layer
+    K.gemm_tn_queue(tn, done=lambda i: ends.pop(i)() if i in ends else None)
+    assert not ends, "engine.run_wgrad_queue: %d layers were never completed" % len(ends)
 
 
 def _param_only(po, fn, src, dst):

@@ -523,6 +523,9 @@ class SegmentedStep:
     def _s_vision_wgrad(self, ci):
         work = self._vq.pop(ci, None)
         self._held.append(work)                # see _s_tail_wgrad
+        # layer pairs as they are (216 unsplit tiles per launch), not engine.run_wgrad_queue: as one queue a stage of four blocks is 256 tiles
+        # + 176, and the split rule cuts those 176 into 4 slices - 180 MB of partial tiles that are not written today, and other low bits
+        # in weights that are computed unsplit now
         for fn in work or ():
             fn()
 
@@ -536,8 +539,7 @@ class SegmentedStep:
         # the next stream-A kernels (eagerly) or to the next stream-A segment's capture while B still reads them.
         work, self._queue = self._queue, None
         self._held.append(work)
-        for fn in work or ():
-            fn()
+        self.engine.run_wgrad_queue(work)      # all fusion layers' GEMMs as one queue: whole rounds unsplit, one split remainder
 
     # ------------------------------------------------------------------ one step
     def _run(self, mode):

@@ -211,15 +211,7 @@ def gemm_tn_grouped(problems, accumulate=False, split=0):
     split: slices of the contraction (0 = the library picks what fills the CUs; partial tiles go through the stream
     workspace and are added deterministically; small launches use the 128x128 kernel, where split > 1 adds atomically and
     needs accumulate=True)."""
-    rows = []
-    for pr in problems:
-        dY, X, dW = pr[:3]
-        assert dY.dtype == BF16 and X.dtype == BF16 and dW.dtype == F32 and dY.shape[0] == X.shape[0]
-        N, K = dW.shape
-        n_ld, k_ld = (pr[3], pr[4]) if len(pr) == 5 else (dY.shape[1], X.shape[1])
-        assert dY.shape[1] >= N or n_ld >= N
-        rows.append([dY.data_ptr(), X.data_ptr(), dW.data_ptr(), dY.shape[0], N, K, _rows(dY), _rows(X), _rows(dW),
-                     n_ld, k_ld])
+    rows = _tn_rows(problems)
     dev = problems[0][0].device
     for i in range(0, len(rows), 8):
         chunk = rows[i:i + 8]
@@ -229,6 +221,78 @@ def gemm_tn_grouped(problems, accumulate=False, split=0):
         ws = workspace(dev, want) if split != 1 else None
         with _timed(sum(2.0 * r[3] * r[4] * r[5] for r in chunk), "gemm_tn"):
             call("x2_gemm_tn_grouped", arr, len(chunk), 1 if accumulate else 0, split, ptr(ws), 0 if ws is None else ws.numel())
+
+
+_CUS = {}
+
+
+def _device_cus(dev):
+    """compute units of the device (x2_device_cus), asked once; 256 where there is none to ask"""
+    if dev not in _CUS:
+        _CUS[dev] = (_lib.lib().x2_device_cus() if dev.type == "cuda" else 0) or 256
+    return _CUS[dev]
+
+
+def _tn_rows(problems):
+    rows = []
+    for pr in problems:
+        dY, X, dW = pr[:3]
+        assert dY.dtype == BF16 and X.dtype == BF16 and dW.dtype == F32 and dY.shape[0] == X.shape[0]
+        N, K = dW.shape
+        n_ld, k_ld = (pr[3], pr[4]) if len(pr) == 5 else (dY.shape[1], X.shape[1])
+        assert dY.shape[1] >= N or n_ld >= N
+        rows.append([dY.data_ptr(), X.data_ptr(), dW.data_ptr(), dY.shape[0], N, K, _rows(dY), _rows(X), _rows(dW), n_ld, k_ld])
+    return rows
+
+
+def tn_plan(shapes, cus=0, ws_floats=0):
+    """The launch plan of a weight-gradient queue (x2_tn_plan: host arithmetic, no GPU): shapes = [(Mc, N, K), ...] ->
+    (windows [(launch, problem, first tile, tile count), ...] in launch order, launches [(split, is_remainder), ...]).
+    cus = 0: the compute units the library plans with."""
+    flat = (C.c_int64 * (3 * len(shapes)))(*[int(v) for s in shapes for v in s])
+    nw, nl = C.c_int(0), C.c_int(0)
+    h = _lib.lib()
+
+    def ask(*a):
+        if h.x2_tn_plan(flat, len(shapes), cus, ws_floats, *a, C.byref(nw), C.byref(nl)) != 0:
+            raise RuntimeError("x2_tn_plan: %s" % h.x2_last_error().decode())
+    ask(None, 0, None, 0)
+    win, lau = (C.c_int * (4 * nw.value))(), (C.c_int * (2 * nl.value))()
+    ask(win, nw.value, lau, nl.value)
+    return ([tuple(win[4 * i:4 * i + 4]) for i in range(nw.value)], [tuple(lau[2 * i:2 * i + 2]) for i in range(nl.value)])
+
+
+def gemm_tn_queue(problems, accumulate=False, done=None):
+    """Weight gradients of a QUEUE of problems (tuples as gemm_tn_grouped takes them; every layer whose operands are ready), planned
+    across layers: whole rounds of the compute units run unsplit, only the tiles left over go through split partial tiles and the
+    fixed-order reducer (x2_gemm_tn_queue).  Problems complete in the order given.  done(i), if given, is called once per problem,
+    in order, right after the launch that holds problem i's last tile has been enqueued - never before it."""
+    rows = _tn_rows(problems)
+    dev = problems[0][0].device
+    arr = (C.c_int64 * (11 * len(rows)))(*[v for r in rows for v in r])
+    tiles = [((r[4] + 255) // 256) * ((r[5] + 255) // 256) for r in rows]
+    # room for 4 slices of the remainder, which has fewer tiles than the device has compute units
+    want = 4 * min(sum(tiles), max(_device_cus(dev) - 1, 1)) * 65536
+    ws = workspace(dev, want)
+    acc = 1 if accumulate else 0
+    flops = sum(2.0 * r[3] * r[4] * r[5] for r in rows)
+    if done is None or sum(tiles) < 24 or _lib.lib().x2_tune_get(5) == 1:         # one call: the whole plan (or the 128x128 kernel's groups)
+        with _timed(flops, "gemm_tn"):
+            call("x2_gemm_tn_queue", arr, len(rows), acc, ptr(ws), want, 0, 0)
+        for i in range(len(rows) if done is not None else 0):
+            done(i)
+        return
+    windows, launches = tn_plan([r[3:6] for r in rows], 0, want)
+    last = {}
+    for launch, prob, _first, _n in windows:
+        last[prob] = launch
+    nxt = 0
+    for l in range(len(launches)):
+        with _timed(flops / len(launches), "gemm_tn"):
+            call("x2_gemm_tn_queue", arr, len(rows), acc, ptr(ws), want, l, 1)
+        while nxt < len(rows) and last[nxt] == l:
+            done(nxt)
+            nxt += 1
 
 
 # ----------------------------------------------------------------------------- attention
