@@ -357,6 +357,24 @@ int x2_vqa_candidates(const long* answer_ids, const long* answer_atts, const int
 int x2_vqa_rerank(const float* loss_rows, int T, const float* vals, const int* ids, int B, int K, float* topk_probs, int* topk_ids, float* scores,
                   void* stream);
 
+/* ---- VQA fine-tune: additive to ABI v14 (csrc/vqa.hip, csrc/gemm.hip) - XVLMForVQA.forward(train=True), models/model_generation.py:517-550:
+ * loss = sum_s weights[s] * (sum_t CE(logits[s][t], answer_ids[s][t+1])) / B.  No existing signature or struct changes, x2_abi_version() stays 14.
+ *   x2_vqa_train_rows : the S answer rows of a batch of B questions; rows offs[b] .. offs[b+1]-1 belong to question b (offs int32 [B+1], the
+ *       exclusive prefix sum of k, read on the device).  kv_idx [S] = that b; labels [S][La-1] = the next token, -100 where it is pad_token_id;
+ *       mask2d as x2_vqa_candidates; c [S] = weights[s] / B.  Rows s >= offs[B] are padding: labels all -100, c = 0, kv_idx = B - 1 (the last
+ *       question); their mask follows their answer_atts like any row's.  2 <= La <= 128.  One writer per element, no atomics.
+ *   x2_seq_loss_combine : second stage of x2_mlm_ce_fwd over rows r = s * T + t (T = La - 1 <= 127): lse [S*T] (x2_ce_combine's bits),
+ *       loss_seq [S] = sum_t (lse - zlab), 0 where labels[r] < 0, added in index order; with c [S] (c and total come together) total [1] =
+ *       sum_s c[s] * loss_seq[s], added in a fixed order by one workgroup.
+ *   x2_mlm_seq_bwd : dl [R][ldd] bf16 = (softmax(z[r]) - onehot(labels[r])) * (c[r / T] * g[0]), z recomputed as x2_mlm_ce_bwd does; exact
+ *       zeros on rows with a negative label, on every row of a sequence whose c[s] * g[0] is 0, and in columns V .. Vp-1.  R % T == 0. */
+int x2_vqa_train_rows(const int* offs, const long* answer_ids, const long* answer_atts, const float* weights, int B, int S, int La,
+                      long pad_token_id, int* kv_idx, long* labels, float* mask2d, int mask2d_ld, float* c, void* stream);
+int x2_seq_loss_combine(const float* part, int chunks, const float* zlab, const long* labels, int S, int T, const float* c, float* lse,
+                        float* loss_seq, float* total, void* stream);
+int x2_mlm_seq_bwd(const void* X, const void* E, const float* bias, const long* labels, const float* c, const float* lse, const float* g, int T,
+                   int R, int Vp, int V, int Hd, int ldx, int lde, void* dl_bf16, long ldd, void* stream);
+
 /* ---- visual grounding: additive to ABI v14 (csrc/grounding.hip) - XVLMForGrounding (models/model_grounding.py), the box tail of
  * XVLMBase.get_bbox_loss + box_ops.py (xvlm.py:927-957) and grounding_eval_bbox / computeIoU (dataset/utils.py:363-453).  No existing signature
  * or struct changes, x2_abi_version() stays 14.  All tensors fp32 (hit: int32), rows of four floats 16-byte aligned (size: 8-byte).

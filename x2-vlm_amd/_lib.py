@@ -95,6 +95,10 @@ _SIGS = {
     "x2_answer_topk": [P, I, I, I, P, I, I, P, P, P],
     "x2_vqa_candidates": [P, P, P, I, I, I, I, L, P, P, P, P, I, P],
     "x2_vqa_rerank": [P, I, P, P, I, I, P, P, P, P],
+    # VQA fine-tune (additive to ABI v14)
+    "x2_vqa_train_rows": [P, P, P, P, I, I, I, L, P, P, P, I, P, P],
+    "x2_seq_loss_combine": [P, I, P, P, I, I, P, P, P, P, P],
+    "x2_mlm_seq_bwd": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, L, P],
     # visual grounding (additive to ABI v14)
     "x2_bbox_loss_fwd": [P, P, P, I, P, P, P],
     "x2_bbox_loss_bwd": [P, P, P, P, P, P, P, I, P, P],

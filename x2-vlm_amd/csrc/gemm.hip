@@ -100,6 +100,7 @@ __device__ __forceinline__ void st16(void* p, u32x4 v, bool wt) {
 //     made the first fused form slower than that pass
 //  11 = 8 plus the chunk sums of the logits and the logit at the ignored class (x2_mlm_ls_fwd: label-smoothed MLM loss, captioning)
 //  12 bias, then (sum(q) softmax - q) * w[row] * g / (sum w + 1e-5) -> bf16, q the smoothed target (x2_mlm_ls_bwd)
+//  13 bias, then (softmax - onehot) * c[row / T] * g -> bf16: gradient of the per-sequence summed cross-entropy (x2_mlm_seq_bwd)
 #ifdef X2_PROBE
 #define NT_DBG(p, bit) (((p).dbg & (bit)) != 0)
 // per-phase time stamps of gemm_nt256_kernel (probe builds only): wave 0 of every workgroup writes wall_clock64() (100 MHz) at
@@ -271,6 +272,18 @@ __device__ __forceinline__ void nt_epilogue(const GemmNT& p, Acc& acc, char* sme
           const float q = c == lab ? conf : (c == p.ce_ignore ? 0.f : sm);
           v[e] = c < p.ce_C ? (qsum * __expf(v[e] - l) - q) * sc : 0.f;
         }
+        st16(reinterpret_cast<bf16_t*>(p.C) + (size_t)m * p.ldc + n,
+             u32x4{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7])}, false);
+        continue;
+      }
+      if constexpr (VAR == 13) {
+        // per-sequence LM loss (x2_mlm_seq_bwd): rows m = s * T + t, T in p.ksplit (no split here; the struct keeps its layout), c[s] in p.ce_w.
+        // (c * g) first: a cotangent vector with g = 1 and a scalar g with the sequence weights give the same bits when the products are equal
+        const long lab = p.ce_labels[m];
+        const float sc = p.ce_w[m / p.ksplit] * p.ce_g[0], l = p.ce_lse[m];
+        const bool live = lab >= 0 && sc != 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = live && n + e < p.ce_C ? (__expf(v[e] - l) - ((long)(n + e) == lab ? 1.f : 0.f)) * sc : 0.f;
         st16(reinterpret_cast<bf16_t*>(p.C) + (size_t)m * p.ldc + n,
              u32x4{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7])}, false);
         continue;
@@ -1467,6 +1480,23 @@ extern "C" int x2_mlm_ls_bwd(const void* X, const void* E, const float* bias, co
            labels, lse, g, stat, nullptr, nullptr, gscale, V, nullptr, nullptr, ignore, ls, w};
   launch_nt_ce(p, 12, (hipStream_t)stream);
   return x2_check_launch("x2_mlm_ls_bwd");
+}
+// Per-sequence form of x2_mlm_ce_bwd (VQA fine-tune: the answer decoder's LM loss, summed per answer; additive to ABI v14).  Rows r = s * T + t:
+// dl[r] = (softmax(z[r]) - onehot(labels[r])) * c[s] * g[0]; exact zeros on rows whose label is negative, on every row of a sequence with
+// c[s] * g[0] == 0 and in the pad columns V .. Vp - 1.  lse is x2_seq_loss_combine's.  GemmNT is left as it is: c travels in ce_w and T in
+// ksplit, which only the split-contraction variant 7 reads; the tile rule is launch_nt_ce's.
+extern "C" int x2_mlm_seq_bwd(const void* X, const void* E, const float* bias, const long* labels, const float* c, const float* lse, const float* g,
+                              int T, int R, int Vp, int V, int Hd, int ldx, int lde, void* dl_bf16, long ldd, void* stream) {
+  X2_REQUIRE(X && E && labels && c && lse && g && dl_bf16, "x2_mlm_seq_bwd: null argument");
+  X2_REQUIRE(mlm_ce_shapes_ok(R, Vp, V, Hd, ldx, lde) && ldd >= Vp && ldd % 8 == 0 && T >= 1 && R % T == 0,
+             "x2_mlm_seq_bwd: R=%d T=%d Vp=%d V=%d Hd=%d ldd=%ld", R, T, Vp, V, Hd, ldd);
+  GemmNT p{(const bf16_t*)X, (const bf16_t*)E, dl_bf16, bias, nullptr, nullptr, nullptr, R, Vp, Hd, ldx, lde, (int)ldd, 0, 0, 0, 0,
+           g_tune[0] > 0 ? g_tune[0] : 8, DropSpec{0u, 0u, 1.f}, nullptr, nullptr, nullptr, 0, T,
+           labels, lse, g, nullptr, nullptr, nullptr, 1.f, V, nullptr, nullptr, 0, 0.f, c};
+  const int tiles_n = (Vp + BN - 1) / BN, t128 = ((R + 127) / 128) * tiles_n, t64 = ((R + 63) / 64) * tiles_n;
+  if (t128 <= 2 * x2_cus()) hipLaunchKernelGGL((gemm_nt_kernel<2, 13>), dim3(t64), dim3(256), 2 * (64 * 128 + TILE_BYTES), (hipStream_t)stream, p);
+  else hipLaunchKernelGGL((gemm_nt_kernel<4, 13>), dim3(t128), dim3(256), GEMM_LDS_BYTES, (hipStream_t)stream, p);
+  return x2_check_launch("x2_mlm_seq_bwd");
 }
 
 // ---------------------------------------------------------------------------------------------

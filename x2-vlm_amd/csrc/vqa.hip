@@ -1,4 +1,5 @@
-// VQA inference (XVLMForVQA.rank_answer, models/model_generation.py:562-619): the three kernels around the two decoder passes.
+// VQA inference (XVLMForVQA.rank_answer, models/model_generation.py:562-619): the three kernels around the two decoder passes, and the
+// two row kernels of the training step (forward(train=True), model_generation.py:517-550) at the end of the file.
 //   x2_answer_topk     log-softmax of the first-step logits, gathered at every candidate answer's first token, k best candidates
 //   x2_vqa_candidates  ids, next-token labels, K/V row map and the additive causal x padding mask of the B * k candidate rows
 //   x2_vqa_rerank      score = first-token log-probability - sum of the per-token losses, softmax over a question's k scores, sorted
@@ -157,4 +158,104 @@ extern "C" int x2_vqa_rerank(const float* loss_rows, int T, const float* vals, c
   X2_REQUIRE(T >= 1 && T <= VQ_MAXLA - 1, "x2_vqa_rerank: La - 1 = %d must be in 1..%d", T, VQ_MAXLA - 1);
   hipLaunchKernelGGL(vqa_rerank_kernel, dim3(B), dim3(VQ_THREADS), 0, (hipStream_t)stream, loss_rows, T, vals, ids, K, topk_probs, topk_ids, scores);
   return x2_check_launch("x2_vqa_rerank");
+}
+
+// ---------------------------------------------------------------------------------------------------------------- training rows
+// XVLMForVQA.forward(train=True): the S answer rows of a batch, rows offs[b] .. offs[b + 1] - 1 belonging to question b (offs = the exclusive
+// prefix sum of k, on the device: nothing about k is known to the host).  One workgroup per row s.  Rows s >= offs[B] are padding (S is a
+// captured shape, sum(k) is not): labels all -100, c = 0, and kv_idx = B - 1, the LAST question - the count below saturates there, and every
+// question keeps at least its own rows.  The mask rule is x2_vqa_candidates': (1 - tril[i][j] * atts[s][j]) * -10000, pad columns 0.
+__global__ __launch_bounds__(VQ_THREADS) void vqa_train_rows_kernel(const int* __restrict__ offs, const long* __restrict__ answer_ids,
+                                                                    const long* __restrict__ answer_atts, const float* __restrict__ weights,
+                                                                    int B, int La, int Lp, long pad_id, int* __restrict__ kv_idx,
+                                                                    long* __restrict__ labels, float* __restrict__ mask2d, float* __restrict__ c) {
+  __shared__ float sAtt[VQ_MAXLA];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const bool real = s < offs[B];
+  const long* src = answer_ids + (size_t)s * La;
+  for (int t = tid; t < La; t += VQ_THREADS) {
+    sAtt[t] = (float)answer_atts[(size_t)s * La + t];
+    if (t + 1 < La) {
+      const long nxt = src[t + 1];
+      labels[(size_t)s * (La - 1) + t] = (!real || nxt == pad_id) ? -100L : nxt;
+    }
+  }
+  if (tid == 0) {
+    int q = 0;                                                             // questions whose range ends at or before s
+    for (int b = 1; b <= B; ++b) q += offs[b] <= s ? 1 : 0;
+    kv_idx[s] = min(q, B - 1);
+    c[s] = real ? weights[s] / (float)B : 0.f;
+  }
+  __syncthreads();
+  float* out = mask2d + (size_t)s * La * Lp;
+  for (int e = tid; e < La * Lp; e += VQ_THREADS) {
+    const int i = e / Lp, j = e - i * Lp;
+    out[e] = j < La ? (1.0f - (j <= i ? sAtt[j] : 0.f)) * -10000.0f : 0.f;
+  }
+}
+
+extern "C" int x2_vqa_train_rows(const int* offs, const long* answer_ids, const long* answer_atts, const float* weights, int B, int S, int La,
+                                 long pad_token_id, int* kv_idx, long* labels, float* mask2d, int mask2d_ld, float* c, void* stream) {
+  X2_REQUIRE(offs && answer_ids && answer_atts && weights && kv_idx && labels && mask2d && c, "x2_vqa_train_rows: null tensor");
+  X2_REQUIRE(B >= 1 && S >= 1, "x2_vqa_train_rows: B=%d S=%d", B, S);
+  X2_REQUIRE(La >= 2 && La <= VQ_MAXLA, "x2_vqa_train_rows: La=%d must be in 2..%d (the 2-D masked attention's limit)", La, VQ_MAXLA);
+  X2_REQUIRE(mask2d_ld >= La && mask2d_ld % 64 == 0 && mask2d_ld <= VQ_MAXLA, "x2_vqa_train_rows: mask2d_ld=%d must be La=%d rounded up to 64",
+             mask2d_ld, La);
+  hipLaunchKernelGGL(vqa_train_rows_kernel, dim3(S), dim3(VQ_THREADS), 0, (hipStream_t)stream, offs, answer_ids, answer_atts, weights, B, La,
+                     mask2d_ld, pad_token_id, kv_idx, labels, mask2d, c);
+  return x2_check_launch("x2_vqa_train_rows");
+}
+
+// ---------------------------------------------------------------------------------------------------------------- per-sequence loss
+// Second stage of x2_mlm_ce_fwd for the answer decoder: rows r = s * T + t, T = La - 1 scored positions per sequence.  One workgroup per
+// sequence; wave w folds the (max, sum exp) chunk pairs of rows t = w, w + 4, ... into lse[r] with x2_ce_combine's arithmetic (same bits)
+// and leaves lse - z[label] (0 on an ignored row) in LDS; thread 0 then adds the T values in index order.  total (with c): one workgroup,
+// thread i adds c[s] * loss_seq[s] for s = i, i + 256, ... in that order, then the row toolkit's fixed tree.
+__global__ __launch_bounds__(VQ_THREADS) void seq_loss_combine_kernel(const float* __restrict__ part, int chunks, const float* __restrict__ zlab,
+                                                                      const long* __restrict__ labels, int T, float* __restrict__ lse,
+                                                                      float* __restrict__ loss_seq) {
+  __shared__ float sRow[VQ_MAXLA];
+  const int s = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int t = wave; t < T; t += ROW_WAVES) {
+    const size_t r = (size_t)s * T + t;
+    const float2* pr = reinterpret_cast<const float2*>(part) + r * chunks;
+    float mx = -INFINITY;
+    for (int ch = lane; ch < chunks; ch += 64) mx = fmaxf(mx, pr[ch].x);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    float se = 0.f;
+    for (int ch = lane; ch < chunks; ch += 64) { const float2 q = pr[ch]; se += q.y * __expf(q.x - mx); }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) se += __shfl_xor(se, o, 64);
+    if (lane == 0) {
+      const float l = mx + logf(se);
+      lse[r] = l;
+      sRow[t] = labels[r] >= 0 ? l - zlab[r] : 0.f;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float acc = 0.f;
+    for (int t = 0; t < T; ++t) acc += sRow[t];
+    loss_seq[s] = acc;
+  }
+}
+__global__ __launch_bounds__(VQ_THREADS) void seq_loss_total_kernel(const float* __restrict__ loss_seq, const float* __restrict__ c, int S,
+                                                                    float* __restrict__ total) {
+  __shared__ float sRed[ROW_WAVES];
+  float acc = 0.f;
+  for (int s = threadIdx.x; s < S; s += VQ_THREADS) acc += c[s] * loss_seq[s];
+  acc = row_block_sum(acc, sRed);
+  if (threadIdx.x == 0) total[0] = acc;
+}
+
+extern "C" int x2_seq_loss_combine(const float* part, int chunks, const float* zlab, const long* labels, int S, int T, const float* c, float* lse,
+                                   float* loss_seq, float* total, void* stream) {
+  X2_REQUIRE(part && zlab && labels && lse && loss_seq, "x2_seq_loss_combine: null tensor");
+  X2_REQUIRE(S >= 1 && chunks >= 1 && (long)S * T < (1L << 31), "x2_seq_loss_combine: S=%d chunks=%d", S, chunks);
+  X2_REQUIRE(T >= 1 && T <= VQ_MAXLA - 1, "x2_seq_loss_combine: La - 1 = %d must be in 1..%d", T, VQ_MAXLA - 1);
+  X2_REQUIRE((c == nullptr) == (total == nullptr), "x2_seq_loss_combine: c and total come together");
+  hipLaunchKernelGGL(seq_loss_combine_kernel, dim3(S), dim3(VQ_THREADS), 0, (hipStream_t)stream, part, chunks, zlab, labels, T, lse, loss_seq);
+  if (c) hipLaunchKernelGGL(seq_loss_total_kernel, dim3(1), dim3(VQ_THREADS), 0, (hipStream_t)stream, loss_seq, c, S, total);
+  return x2_check_launch("x2_seq_loss_combine");
 }

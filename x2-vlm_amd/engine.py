@@ -1164,6 +1164,72 @@ class MlmLossFn(torch.autograd.Function):
         return drows, None, None, None, ddw, dbd, dlnw, dlnb, dbias[:V], dword, None
 
 
+def _lm_head_backward(dl, rb, t_pre, t_act, mean, rstd, tb, dw_, lnw, word, EbT):
+    """Everything downstream of the logit gradient dl bf16 [R, Vp], for SeqLmLossFn: decoder-bias column sums, the row gradient through the
+    tied decoder (split contraction), LayerNorm / GELU backward of the transform, the dense input gradient and the grouped TN GEMM of the
+    word-embedding and dense weight gradients.  The same launches in the same order as the tail of MlmLossFn.backward, which keeps its own
+    statement of them (the pre-training step's code is left as it was); the two must change together.
+    -> (drows fp32 [R, Hd], ddw, dbd, dlnw, dlnb, dbias [V], dword - None when it was parked for the embedding backward, TIE_WORD_GRAD)."""
+    R, Hd = rb.shape
+    V, Vp = word.shape[0], dl.shape[1]
+    zeros = torch.zeros(Vp + 3 * Hd, device=rb.device, dtype=F32)          # one fill: decoder-bias gradient + the three head vectors below
+    dbias, small = zeros[:Vp], zeros[Vp:]
+    K.colsum_bf16(dl, dbias)
+    # [R, Hd] from a 30528-long contraction: 36-72 output tiles, so the contraction is split (354 -> ~50 us)
+    dt = K.gemm_nt_splitk(dl, EbT)
+    dword = torch.empty_like(word)
+    dlnw, dlnb, dbd = small[:Hd], small[Hd:2 * Hd], small[2 * Hd:]
+    dact, _ = K.layernorm_bwd(dt, t_act, mean, rstd, lnw, dlnw, dlnb)
+    dpre = K.gelu_f32(t_pre.float(), dact)                        # small [R,Hd]: GELU' on the saved pre-activation
+    dpre_b = K.cast_bf16(dpre)
+    K.colsum_bf16(dpre_b, dbd)
+    _, wdT = BANK.linear(dw_)
+    drows = K.gemm_nt(dpre_b, wdT, out_dtype=F32)
+    ddw = torch.empty_like(dw_)
+    K.gemm_tn_grouped([(dl, tb, dword, Vp, Hd), (dpre_b, rb, ddw)])
+    if TIE_WORD_GRAD:
+        _TIED_DWORD[_tok(word)] = dword
+        dword = None
+    return drows, ddw, dbd, dlnw, dlnb, dbias[:V], dword
+
+
+class SeqLmLossFn(torch.autograd.Function):
+    """rows (S * T, Hd) fp32, the T = La - 1 scored positions of S answer rows -> the causal LM loss summed per sequence (xbert.py:1373-1387
+    with reduction='none'; the VQA fine-tune's answer decoder).  Returns (loss_seq fp32 [S], total):
+      c None       loss_seq is the differentiable output (any cotangent [S]), total is None
+      c fp32 [S]   total = sum_s c[s] * loss_seq[s], a differentiable scalar (model_generation.py:547-548 with c = weights / B); loss_seq is
+                   returned for inspection and carries no gradient
+    Transform and tied decoder as MlmLossFn; the logits stay in the decoder GEMM both ways (x2_mlm_ce_fwd + x2_seq_loss_combine, x2_mlm_seq_bwd)
+    and everything downstream of the logit gradient is _lm_head_backward, the launches of MlmLossFn.backward's tail."""
+
+    @staticmethod
+    def forward(ctx, rows, labels, T, c, eps, dw_, db_, lnw, lnb, dec_bias, word):
+        rb = K.cast_bf16(rows.contiguous())
+        tb, t_pre, t_act, mean, rstd, Eb, _, bias_p = lm_head_transform(rb, eps, dw_, db_, lnw, lnb, dec_bias, word)
+        labels = labels.contiguous().view(-1)
+        loss_seq, total, lse = K.mlm_seq_fwd(tb, Eb, bias_p, labels, word.shape[0], T, c)
+        ctx.save_for_backward(rb, t_pre, t_act, mean, rstd, tb, bias_p, labels, lse, dw_, lnw, word, *(() if c is None else (c,)))
+        ctx.T, ctx.weighted = T, c is not None
+        loss_seq = loss_seq.clone()
+        if c is None:
+            return loss_seq, None
+        ctx.mark_non_differentiable(loss_seq)
+        return loss_seq, total[0].clone()
+
+    @staticmethod
+    def backward(ctx, g_seq, g_total):
+        rb, t_pre, t_act, mean, rstd, tb, bias_p, labels, lse, dw_, lnw, word = ctx.saved_tensors[:12]
+        BANK.note_backward()
+        Eb, EbT = BANK.vocab(word)
+        if ctx.weighted:
+            c, g = ctx.saved_tensors[12], g_total.reshape(1).to(F32).contiguous()
+        else:
+            c, g = g_seq.to(F32).contiguous(), torch.ones(1, device=rb.device, dtype=F32)
+        dl = K.mlm_seq_bwd(tb, Eb, bias_p, labels, c, lse, g, word.shape[0], ctx.T)
+        drows, ddw, dbd, dlnw, dlnb, dbias, dword = _lm_head_backward(dl, rb, t_pre, t_act, mean, rstd, tb, dw_, lnw, word, EbT)
+        return drows, None, None, None, None, ddw, dbd, dlnw, dlnb, dbias, dword
+
+
 # ----------------------------------------------------------------------------- small differentiable ops (heads)
 
 class LinearF32Fn(torch.autograd.Function):

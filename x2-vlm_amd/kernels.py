@@ -1021,6 +1021,58 @@ def vqa_rerank(loss_rows, vals, ids):
     return probs, out_ids, scores
 
 
+# ----------------------------------------------------------------------------- VQA fine-tune (csrc/vqa.hip, csrc/gemm.hip)
+
+def vqa_train_rows(offs, answer_ids, answer_atts, weights, pad_token_id):
+    """The answer rows of a training batch in one launch: offs int32 [B + 1] (exclusive prefix sum of k, device), answer_ids / answer_atts int64
+    [S, La], weights fp32 [S] -> (kv_idx int32 [S] the row's question, labels int64 [S, La - 1] (next token, -100 at padding), mask2d fp32
+    [S, La, round_up(La, 64)] the additive tril x padding mask of attn_fwd_mask2d, c fp32 [S] = weights / B).  Rows s >= offs[B] are padding:
+    labels -100, c = 0, kv_idx = B - 1."""
+    assert offs.dtype == torch.int32 and offs.dim() == 1 and offs.is_contiguous() and offs.numel() >= 2
+    assert answer_ids.dtype == torch.int64 and answer_ids.dim() == 2 and answer_ids.is_contiguous()
+    assert answer_atts.dtype == torch.int64 and answer_atts.shape == answer_ids.shape and answer_atts.is_contiguous()
+    S, La = answer_ids.shape
+    assert weights.dtype == F32 and weights.numel() == S and weights.is_contiguous()
+    B, dev = offs.numel() - 1, answer_ids.device
+    kv_idx = torch.empty(S, device=dev, dtype=torch.int32)
+    labels = torch.empty(S, max(La - 1, 0), device=dev, dtype=torch.int64)
+    mask2d = torch.empty(S, La, round_up(La, 64), device=dev, dtype=F32)
+    c = torch.empty(S, device=dev, dtype=F32)
+    call("x2_vqa_train_rows", ptr(offs), ptr(answer_ids), ptr(answer_atts), ptr(weights), B, S, La, int(pad_token_id), ptr(kv_idx), ptr(labels),
+         ptr(mask2d), mask2d.shape[2], ptr(c))
+    return kv_idx, labels, mask2d, c
+
+
+def mlm_seq_fwd(x, E, bias, labels, V, T, c=None):
+    """Per-sequence cross-entropy of z = x @ E^T + bias over the first V columns without storing z: rows r = s * T + t of x [S * T, Hd] bf16,
+    labels int64 [S * T] (negative: ignored) -> (loss_seq fp32 [S] = sum_t (lse - z[label]) in index order, total fp32 [1] =
+    sum_s c[s] * loss_seq[s] or None without c, lse fp32 [S * T])."""
+    assert x.dtype == BF16 and E.dtype == BF16 and x.shape[1] == E.shape[1] and bias.dtype == F32 and bias.numel() == E.shape[0]
+    assert labels.dtype == torch.int64 and labels.numel() == x.shape[0] and x.shape[0] % T == 0
+    R, Hd = x.shape
+    S, Vp, dev = R // T, E.shape[0], x.device
+    assert c is None or (c.dtype == F32 and c.numel() == S and c.is_contiguous())
+    part = torch.empty(R, Vp // 64, 2, device=dev, dtype=F32)
+    small = torch.empty(2 * R + S + 1, device=dev, dtype=F32)
+    zlab, lse, loss_seq, total = small[:R], small[R:2 * R], small[2 * R:2 * R + S], small[2 * R + S:]
+    with _timed(2.0 * R * Vp * Hd):
+        call("x2_mlm_ce_fwd", ptr(x), ptr(E), ptr(bias), ptr(labels), R, Vp, V, Hd, _rows(x), _rows(E), ptr(part), ptr(zlab))
+    call("x2_seq_loss_combine", ptr(part), Vp // 64, ptr(zlab), ptr(labels), S, T, ptr(c), ptr(lse), ptr(loss_seq), ptr(total) if c is not None else None)
+    return loss_seq, (total if c is not None else None), lse
+
+
+def mlm_seq_bwd(x, E, bias, labels, c, lse, g, V, T):
+    """dlogits bf16 [S * T, Vp] of sum_s c[s] * loss_seq[s] times the device scalar g [1] (logits recomputed in the GEMM, never stored): exact
+    zeros on ignored rows, on the rows of a sequence with c[s] * g == 0 and in the pad columns."""
+    R, Hd = x.shape
+    Vp = E.shape[0]
+    assert c.dtype == F32 and c.numel() * T == R and c.is_contiguous() and g.dtype == F32 and g.numel() == 1
+    dl = torch.empty(R, Vp, device=x.device, dtype=BF16)
+    with _timed(2.0 * R * Vp * Hd, "gemm_nt_recompute"):
+        call("x2_mlm_seq_bwd", ptr(x), ptr(E), ptr(bias), ptr(labels), ptr(c), ptr(lse), ptr(g), T, R, Vp, V, Hd, _rows(x), _rows(E), ptr(dl), Vp)
+    return dl
+
+
 # ----------------------------------------------------------------------------- visual grounding (csrc/grounding.hip)
 
 def _box_rows(t, name):

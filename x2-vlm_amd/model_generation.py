@@ -1,9 +1,12 @@
-"""Captioning fine-tune and inference, VQA answer ranking on the MI355X stages (models/model_generation.py:54-619, Captioning_MLM.py, VQA.py).
+"""Captioning fine-tune and inference, VQA fine-tune and answer ranking on the MI355X stages (models/model_generation.py:54-619,
+Captioning_MLM.py, VQA.py).
 
   XVLMForMLMCaptioning   training forward: the label-smoothed, weight-normalised MLM loss of the UniLM-style captioning collate
                          generate / beam_search: beam search over cached K/V (decode.py), HIP device only
-  XVLMForVQA             forward(train=False) / rank_answer: the k candidate answers with the likeliest first token, re-ranked by the
-                         answer decoder's sequence log-probability, HIP device only; the training step is not built yet
+  XVLMForVQA             forward(train=True): the weighted per-answer LM loss of the answer decoder, the question states shared by a
+                         question's answer rows, HIP device only
+                         forward(train=False) / rank_answer: the k candidate answers with the likeliest first token, re-ranked by the
+                         answer decoder's sequence log-probability, HIP device only
 
 The text encoder runs every layer with the collate's [B, L, L] attention mask (tril, or FG-free: [MASK] columns zeroed but for their
 own diagonal entry) through the 2-D masked attention kernels, embeds explicit (repeating) position ids, and forms the loss inside the
@@ -188,7 +191,18 @@ class XVLMForVQA(XVLMBase):
       5. the head's transform and kernels.mlm_ce_rows on positions 0 .. La - 2 of every row: loss per scored token, logits never stored
       6. kernels.vqa_rerank: score = first-token log-probability - summed losses, softmax over k, sorted.
     Ties (candidates sharing a first token tie exactly in stage 2): the lower candidate index / slot comes first, where torch.topk leaves
-    the order open."""
+    the order open.
+
+    The training step (forward(train=True), model_generation.py:517-550), no host synchronisation either:
+      1. kernels.vqa_train_rows: from the prefix sum of k the row -> question map, the next-token labels, the additive tril x padding mask
+         and c = weights / B of the S answer rows, in one launch
+      2. ONE decoder pass over the S rows, the B question states shared through kv_idx (the reference stacks k[b] copies of each); their
+         gradient comes back summed over a question's rows
+      3. engine.SeqLmLossFn: the per-answer summed cross-entropy and sum_s c[s] * loss[s] from softmax statistics reduced inside the decoder
+         GEMM; the backward recomputes the GEMM and writes the logit gradient as bf16.
+    Extension over the reference: with k a DEVICE tensor, rows s >= sum(k) are padding (a captured graph has a fixed S while sum(k) changes
+    from batch to batch): they need valid token ids, get weight 0, no labels and the last question's states, and add exactly zero to the loss
+    and to every gradient."""
 
     def __init__(self, config):
         if config["text_encoder"] == "data/roberta-base":
@@ -255,13 +269,19 @@ class XVLMForVQA(XVLMBase):
         return _load_pretrained(self, ckpt_rpath, config, is_eval, remap, hide="vision_encoder")
 
     def forward(self, image, quesiton, answer=None, k=None, weights=None, train=True, _fused=True, _stage1_ids=None, _return_traces=False):
-        """train=False: (topk_ids int64 [B, k] indices into the answer list, topk_probs fp32 [B, k]) for `image` [B, 3, R, R], the tokenised
+        """train=True: the loss of the reference's training step, a differentiable fp32 device scalar:
+            sum_s weights[s] * (sum over t of CE(logits[s, t], answer_ids[s, t + 1])) / image.size(0)
+        `answer` (.input_ids / .attention_mask [S, La], 2 <= La <= 128) holds one row per (question, answer) pair, the k[b] rows of question b
+        next to each other; a next token equal to pad_token_id is not scored; weights is fp32 [S] and gets no gradient.  k is a list or host
+        tensor (checked: one entry >= 1 per image, sum(k) == S) or a device int tensor [B] that is never read back: the caller guarantees
+        k[b] >= 1 and sum(k) <= S, and rows s >= sum(k) are padding (see the class docstring).  self.training decides the dropout.
+
+        train=False: (topk_ids int64 [B, k] indices into the answer list, topk_probs fp32 [B, k]) for `image` [B, 3, R, R], the tokenised
         questions (`quesiton`, the reference's spelling: .input_ids / .attention_mask [B, Lq]) and the tokenised answer LIST `answer`
         ([Na, La], every row starting with the same start token).  Runs in eval mode under no_grad; the training flag is restored.  The
         underscored keywords are rank_answer's test seam."""
         if train:
-            raise NotImplementedError("XVLMForVQA.forward(train=True): the VQA training step (weighted per-sequence LM loss and its backward) "
-                                      "is the follow-up to answer ranking and is not implemented")
+            return self._train_step(image, quesiton, answer, k, weights)
         ops.require_hip(image, "XVLMForVQA.forward")
         with _inference(self):
             image_embeds, image_atts = self.get_vision_embeds(image)
@@ -269,6 +289,43 @@ class XVLMForVQA(XVLMBase):
                                                 encoder_attention_mask=image_atts, return_dict=True).last_hidden_state
             return self.rank_answer(question_states, quesiton.attention_mask, answer.input_ids, answer.attention_mask, k, _fused=_fused,
                                     _stage1_ids=_stage1_ids, _return_traces=_return_traces)
+
+    def _train_step(self, image, quesiton, answer, k, weights):
+        ops.require_hip(image, "XVLMForVQA.forward(train=True): the VQA training step")
+        B = image.size(0)
+
+        def refuse(what):
+            return NotImplementedError("XVLMForVQA.forward(train=True): the VQA training step takes one k per image and one weight per answer "
+                                       "row, answers of 2 to 128 tokens; got " + what)
+        if answer is None or k is None or weights is None:
+            raise refuse("answer, k or weights missing")
+        dev = image.device
+        answer_ids = answer.input_ids.to(dev).to(torch.int64).contiguous()
+        answer_atts = answer.attention_mask.to(dev).to(torch.int64).contiguous()
+        if answer_ids.dim() != 2 or answer_atts.shape != answer_ids.shape or not 2 <= answer_ids.shape[1] <= 128:
+            raise refuse("answer ids %s, attention mask %s" % (tuple(answer_ids.shape), tuple(answer_atts.shape)))
+        S = answer_ids.shape[0]
+        weights = torch.as_tensor(weights, dtype=torch.float32).detach().to(dev).reshape(-1).contiguous()
+        if weights.numel() != S:
+            raise refuse("%d weights for %d answer rows" % (weights.numel(), S))
+        if isinstance(k, torch.Tensor) and k.is_cuda:
+            if k.numel() != B or k.dtype not in (torch.int32, torch.int64):
+                raise refuse("k of %d %s entries for %d images" % (k.numel(), k.dtype, B))
+            offs = torch.zeros(B + 1, device=dev, dtype=torch.int32)
+            offs[1:] = torch.cumsum(k.reshape(-1), 0)
+        else:
+            ks = [int(n) for n in (k.tolist() if isinstance(k, torch.Tensor) else k)]
+            if len(ks) != B or min(ks) < 1 or sum(ks) != S:
+                raise refuse("k = %s for %d images and %d answer rows" % (ks, B, S))
+            offs = torch.tensor([sum(ks[:b]) for b in range(B + 1)], dtype=torch.int32).to(dev)
+        image_embeds, image_atts = self.get_vision_embeds(image)
+        question_states = self.text_encoder(quesiton.input_ids, attention_mask=quesiton.attention_mask, encoder_hidden_states=image_embeds,
+                                            encoder_attention_mask=image_atts, return_dict=True).last_hidden_state
+        kv_idx, labels, mask2d, c = K.vqa_train_rows(offs, answer_ids, answer_atts, weights, self.pad_token_id)
+        row_atts = quesiton.attention_mask.index_select(0, kv_idx.long())
+        out = self.text_decoder(answer_ids, encoder_hidden_states=question_states.contiguous(), encoder_attention_mask=row_atts, kv_idx=kv_idx,
+                                self_mask2d=mask2d, reduction="none", _next_labels=labels, _seq_weights=c)
+        return out.total
 
     def rank_answer(self, question_states, question_atts, answer_ids, answer_atts, k, _fused=True, _stage1_ids=None, _return_traces=False):
         """question_states [B, Lq, Hd] fp32, question_atts [B, Lq], answer_ids / answer_atts int64 [Na, La] -> (topk_ids int64 [B, k],

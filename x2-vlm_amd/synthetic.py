@@ -273,3 +273,40 @@ def synth_vqa_batch(seed, batch, seq_len, image_res, vocab_size, n_answers, answ
         atts[a, :n] = 1
     return dict(image=base["image"], question_ids=base["text_ids"], question_atts=base["text_atts"], answer_ids=torch.from_numpy(ids),
                 answer_atts=torch.from_numpy(atts))
+
+
+def synth_vqa_train_batch(seed, batch, seq_len, image_res, vocab_size, k, answer_len):
+    """VQA training batch: `batch` images and ragged questions as synth_vqa_batch (synth_batch's under `seed`) and sum(k) answer rows, k[b] of
+    them for question b, next to each other: [CLS] t1 .. tn [SEP] padded with 0 to answer_len, lengths 3 .. answer_len (the first row has the
+    full length), no two rows of one question equal; weights drawn from {0.3, 0.6, 0.9, 1.0} as VQA v2's soft scores are.  Returns a dict of CPU
+    tensors: image, question_ids / question_atts (batch, seq_len), answer_ids / answer_atts (sum(k), answer_len) int64, weights fp32 (sum(k),),
+    k int64 (batch,)."""
+    k = [int(n) for n in k]
+    if len(k) != batch or min(k) < 1 or answer_len < 3:
+        raise ValueError("synth_vqa_train_batch: k = %s for %d images, answer_len %d" % (k, batch, answer_len))
+    base = synth_batch(seed, batch, seq_len, image_res, vocab_size, max_masks=1, ragged=True)
+    r = _rng(seed, "vqa_train_answers")
+    big = vocab_size > 2000
+    cls_id, sep_id = (101, 102) if big else (1, 2)
+    lo = 1000 if big else 5
+    S = sum(k)
+    ids = np.zeros((S, answer_len), dtype=np.int64)
+    atts = np.zeros((S, answer_len), dtype=np.int64)
+    s = 0
+    for n_rows in k:
+        seen = set()
+        for _ in range(n_rows):
+            for _try in range(1000):
+                n = answer_len if s == 0 else int(r.integers(3, answer_len + 1))
+                row = [cls_id] + [int(t) for t in r.integers(lo, vocab_size, size=n - 2)] + [sep_id]
+                if tuple(row) not in seen:
+                    break
+            else:
+                raise ValueError("synth_vqa_train_batch: no distinct row found for answer row %d" % s)
+            seen.add(tuple(row))
+            ids[s, :n] = row
+            atts[s, :n] = 1
+            s += 1
+    weights = np.array([0.3, 0.6, 0.9, 1.0], dtype=np.float32)[r.integers(0, 4, size=S)]
+    return dict(image=base["image"], question_ids=base["text_ids"], question_atts=base["text_atts"], answer_ids=torch.from_numpy(ids),
+                answer_atts=torch.from_numpy(atts), weights=torch.from_numpy(weights), k=torch.tensor(k, dtype=torch.int64))

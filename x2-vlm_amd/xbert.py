@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from . import kernels as K
 from . import ops
-from .engine import BertLayersFn, EmbeddingsFn, MlmLossFn, _mask_pad, bert_layer_param_names, lm_head_transform
+from .engine import BertLayersFn, EmbeddingsFn, MlmLossFn, SeqLmLossFn, _mask_pad, bert_layer_param_names, lm_head_transform
 
 
 _FIXED_SEEDS = []
@@ -321,8 +321,8 @@ class BertForMaskedLM(nn.Module, LMHeadRows):
 class BertLMHeadModel(nn.Module, LMHeadRows):
     """xbert.py:1268-1400, the causal answer decoder of XVLMForVQA: `bert` with cross-attention in every layer (config.fusion_layer = 0,
     config.encoder_width = the question states' width) and the LM head `cls`, whose decoder.weight is tied to ITS OWN word embeddings.
-    Built for answer ranking (inference): forward returns the hidden states of a causal pass; head_logits / head_loss_rows apply the head
-    to gathered rows.  The LM loss of forward(labels=...) - the training step - is not implemented and refused."""
+    forward returns the hidden states of a causal pass and, with labels, the next-token LM loss formed inside the decoder GEMM (HIP tensors
+    only; label smoothing and return_logits are refused); head_logits / head_loss_rows apply the head to gathered rows at inference."""
 
     def __init__(self, config, label_smoothing=0.0):
         super().__init__()
@@ -337,21 +337,65 @@ class BertLMHeadModel(nn.Module, LMHeadRows):
     def get_output_embeddings(self):
         return self.cls.predictions.decoder
 
-    def forward(self, input_ids=None, attention_mask=None, encoder_hidden_states=None, encoder_attention_mask=None, return_dict=True,
-                is_decoder=True, reduction="mean", mode="multi_modal", kv_idx=None, self_mask2d=None, **unused):
+    def forward(self, input_ids=None, attention_mask=None, encoder_hidden_states=None, encoder_attention_mask=None, labels=None, return_dict=True,
+                is_decoder=True, reduction="mean", mode="multi_modal", kv_idx=None, self_mask2d=None, _next_labels=None, _seq_weights=None,
+                **unused):
         """-> last_hidden_state [S, L, Hd] of the causal pass.  The self-attention mask is tril x attention_mask [S, L] (None: ones), or
-        the additive self_mask2d kernels.vqa_candidates built from the same rule; encoder_hidden_states [Bq, T, Hd] may be shared by
-        several rows through kv_idx, encoder_attention_mask is per row [S, T]."""
+        the additive self_mask2d kernels.vqa_candidates / vqa_train_rows built from the same rule; encoder_hidden_states [Bq, T, Hd] may be
+        shared by several rows through kv_idx, encoder_attention_mask is per row [S, T].
+
+        labels int64 [S, L], -100 where ignored (xbert.py:1373-1387): position t is scored against labels[:, t + 1], t = 0 .. L - 2, and the
+        result also carries .loss - reduction='none': fp32 [S], the sum over a row's scored positions, differentiable for any cotangent;
+        reduction='mean': the mean over the non-ignored tokens (NaN when there is none, as CrossEntropyLoss gives).  The logits are never stored;
+        return_dict=False gives (loss, last_hidden_state).
+        Not part of the mirrored signature (XVLMForVQA's training step): _next_labels int64 [S, L - 1], the already shifted labels in labels'
+        place; _seq_weights fp32 [S] adds .total = sum_s _seq_weights[s] * loss[s], then THE differentiable output (.loss carries no gradient)."""
         _refuse_unused("BertLMHeadModel", unused)
         if not is_decoder:
             raise NotImplementedError("BertLMHeadModel.forward(is_decoder=False) is not supported by the HIP path")
+        with_loss = labels is not None or _next_labels is not None
+        if with_loss:
+            ops.require_hip(input_ids, "BertLMHeadModel.forward(labels=...): the LM loss")
+            if self.label_smoothing > 0:
+                raise NotImplementedError("BertLMHeadModel.forward(labels=...) with label_smoothing > 0 is not implemented (the smoothed head "
+                                          "is the captioning model's)")
+            if reduction not in ("mean", "none"):
+                raise ValueError("BertLMHeadModel.forward: reduction=%r (mean or none)" % (reduction,))
         S, L = input_ids.shape
+        if with_loss and L < 2:
+            raise ValueError("BertLMHeadModel.forward(labels=...): %d position leaves no next token to score" % L)
         if self_mask2d is None and L > 1:
             atts = torch.ones(S, L, dtype=torch.long, device=input_ids.device) if attention_mask is None else attention_mask.long()
             attention_mask = torch.tril(torch.ones(L, L, dtype=torch.long, device=input_ids.device)).unsqueeze(0) * atts.unsqueeze(1)
         h = self.bert(input_ids, attention_mask=attention_mask, encoder_hidden_states=encoder_hidden_states,
                       encoder_attention_mask=encoder_attention_mask, mode=mode, kv_idx=kv_idx, self_mask2d=self_mask2d).last_hidden_state
-        return SimpleNamespace(last_hidden_state=h) if return_dict else (h,)
+        if not with_loss:
+            return SimpleNamespace(last_hidden_state=h) if return_dict else (h,)
+        nxt = _next_labels if _next_labels is not None else labels[:, 1:]
+        nxt = nxt.to(torch.int64).reshape(-1).contiguous()
+        rows = ops.gather_rows(h.reshape(S * L, -1), self._scored_rows(S, L, h.device))
+        pr = self.cls.predictions
+        head = (self.config.layer_norm_eps, pr.transform.dense.weight, pr.transform.dense.bias, pr.transform.LayerNorm.weight,
+                pr.transform.LayerNorm.bias, pr.bias, self.bert.embeddings.word_embeddings.weight)
+        total = None
+        if reduction == "none" or _seq_weights is not None:
+            loss, total = SeqLmLossFn.apply(rows, nxt, L - 1, _seq_weights, *head)
+        else:
+            loss = MlmLossFn.apply(rows, nxt, head[0], False, *head[1:])[0]
+        if not return_dict:
+            return (loss, h)
+        return SimpleNamespace(loss=loss, total=total, last_hidden_state=h)
+
+    def _scored_rows(self, S, L, dev):
+        """int32 [S * (L - 1)]: the flat positions 0 .. L - 2 of every row of [S, L]"""
+        cache = self.__dict__.setdefault("_scored_rows_idx", {})
+        rows = cache.get((S, L, dev))
+        if rows is None:
+            rows = (torch.arange(S, device=dev, dtype=torch.int32).unsqueeze(1) * L
+                    + torch.arange(L - 1, device=dev, dtype=torch.int32)).reshape(-1).contiguous()
+            if not torch.cuda.is_current_stream_capturing():          # a tensor born inside a capture belongs to that graph's pool
+                cache[(S, L, dev)] = rows
+        return rows
 
 
 def _refuse_unused(who, unused):
