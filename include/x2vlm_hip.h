@@ -464,6 +464,38 @@ int x2_kl_ce_bwd(const float* logits, int ldl, const float* teacher, int ldt, in
                  const float* g_logits, int ldg, void* dl, int lddl, int Cp, void* stream);
 int x2_cls_accuracy_rows(const float* logits, int ldl, const long* labels, int R, int C, int* pred, int* hit, long* counts, void* stream);
 
+/* ---- image-text retrieval fine-tune and evaluation: additive to ABI v14 (csrc/retrieval.hip) - XVLMForRetrieval (models/model_retrieval.py), the
+ * soft-label branch of XVLMBase.get_contrastive_loss (xvlm.py:805-826), get_hard_negatives with `idx` (xvlm.py:828-857) and itm_eval
+ * (Retrieval.py:171-215).  No existing signature or struct changes, x2_abi_version() stays 14.  fp32 tensors except idx / group / counts (int64) and
+ * out / no_negative / gt_offs / gt_ids / ranks (int32).  Plain fp32 arithmetic with libm expf / logf, no atomics, one writer per output element,
+ * fixed summation orders (file header): two runs give the same bits.
+ *   x2_itc_soft_fwd : logits [N][ld] = the similarities already divided by temp, idx [N] the (all-gathered) group ids, pos_ij = (idx[i] == idx[j]).
+ *       2 <= N <= 1024 (x2_sample_negatives' bound), ld >= N; columns [N, ld) are never read.  Launch one, N + ceil(N / 64) workgroups: per row i
+ *       cnt_i = sum_j pos_ij, lse_i = max + log sum exp(z_ij - max), li_i = lse_i - (sum_j pos_ij z_ij) / cnt_i; per column j the same over z_.j
+ *       (lt_j), the matrix read row-major by workgroups of 64 adjacent columns - no transpose, no strided walk.  rowstat / colstat [N][3] =
+ *       {max, log sum exp(z - max), cnt} (lse = the sum of the first two, kept apart: one fp32 lse near 1000, at temp = 0.001, is too coarse for
+ *       the backward's exp(z - lse)), loss_rows [2N] = {li, lt}.  Launch two, one workgroup: out[0] = (sum_i li_i / N + sum_j lt_j / N) / 2.
+ *   x2_itc_soft_bwd : one launch, a workgroup per row: dlogits[i][j] = g[0] / (2N) * ((exp(z_ij - lse_i) - pos_ij / cnt_i) + (exp(z_ij - lse^col_j)
+ *       - pos_ij / cnt_j)) for j < N; g a device scalar; rowstat / colstat are the forward's; ldd >= N, columns [N, ldd) are not written.
+ *   x2_sample_negatives_checked : x2_sample_negatives - the same device function, the same arithmetic and tie handling, bit for bit - plus
+ *       no_negative [n] = 1 where every candidate of row b is masked (all rows share its group) or none has a positive weight (a row of NaN
+ *       similarities), else 0; out[b] = b on such a row.
+ *   x2_retrieval_ranks : scores [R][ld], N columns (1 <= N <= 65536, ld >= N, R >= 1); the ground-truth columns of query r are
+ *       gt_ids[gt_offs[r] .. gt_offs[r+1]) (CSR; the caller guarantees 0 <= gt_offs[r] <= gt_offs[r+1] <= the length of gt_ids); an id outside
+ *       [0, N) is skipped and never dereferenced.  Launch one, a workgroup per row: ranks[r] = min over its ground truths j of
+ *       #{c < N : s[c] > s[j]} - STRICTLY greater: the tie rule.  np.argsort(...)[::-1] has no defined order among equal scores, so this is the
+ *       reference's rank whenever the ground truth's score is not tied; with rerank_scores' -100 fill a ground truth outside the top k_test gets
+ *       rank k_test here and some rank >= k_test there, so R@1 / R@5 / R@10 agree for k_test >= 10.  A row without a ground truth gets INT_MAX
+ *       (the reference's 1e20): in no recall, but in the denominator.  Launch two, one workgroup: counts [4] += {#ranks < 1, #ranks < 5,
+ *       #ranks < 10, R} by a plain read-modify-write (the caller zeroes counts once; launches on one stream accumulate).  NaN scores are outside
+ *       the contract.
+ * An argument outside its range returns -1 and names the entry point in x2_last_error() without launching. */
+int x2_itc_soft_fwd(const float* logits, int ld, const long* idx, int N, float* rowstat, float* colstat, float* loss_rows, float* out, void* stream);
+int x2_itc_soft_bwd(const float* logits, int ld, const long* idx, int N, const float* rowstat, const float* colstat, const float* g, float* dlogits,
+                    int ldd, void* stream);
+int x2_sample_negatives_checked(const float* sim, int n, const long* group, const float* u, int* out, int* no_negative, void* stream);
+int x2_retrieval_ranks(const float* scores, int ld, int R, int N, const int* gt_offs, const int* gt_ids, int* ranks, long* counts, void* stream);
+
 /* ---- optimizer (csrc/optim.hip) -- "next" row of the scope table ------------------------------------------
  * optim.py:26-104 (transformers==4.12.5 AdamW, eps 1e-8, betas (0.9,0.98), correct_bias) and the global-norm clip of
  * accelerators/apex_ddp_accelerator.py:99-102, as two multi-tensor launches.  table: ntensors records

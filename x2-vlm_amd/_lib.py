@@ -115,6 +115,11 @@ _SIGS = {
     "x2_soft_ce_bwd": [P, I, I, I, P, P, P, P, P, P, P, I, P, I, I, P],
     "x2_kl_ce_bwd": [P, I, P, I, I, I, P, P, P, P, I, P, I, I, P],
     "x2_cls_accuracy_rows": [P, I, P, I, I, P, P, P, P],
+    # image-text retrieval fine-tune and evaluation: XVLMForRetrieval (additive to ABI v14)
+    "x2_itc_soft_fwd": [P, I, P, I, P, P, P, P, P],
+    "x2_itc_soft_bwd": [P, I, P, I, P, P, P, P, I, P],
+    "x2_sample_negatives_checked": [P, I, P, P, P, P, P],
+    "x2_retrieval_ranks": [P, I, I, I, P, P, P, P, P],
 }
 # communicator entry points (csrc/comm.hip): explicit stream / event arguments, bound without the implicit stream of call()
 _COMM_SIGS = {

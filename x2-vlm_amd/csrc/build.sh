@@ -7,7 +7,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
 if [ "$1" = "--clean" ]; then rm -rf ../_build $OUT; fi     # every object from source (a driver proving a from-source build: X2_CLEAN_BUILD=1)
 mkdir -p ../_build
 pids=()
-for f in runtime gemm attention rowwise heads masking optim comm decode vqa grounding classify classify_wide; do
+for f in runtime gemm attention rowwise heads masking optim comm decode vqa grounding classify classify_wide retrieval; do
   newest=$(ls -t $f.hip *.h | head -1)                       # every header counts: any of them may reach any object
   if [ ! -f ../_build/$f.o ] || [ $newest -nt ../_build/$f.o ]; then
     hipcc $FLAGS -c $f.hip -o ../_build/$f.o &

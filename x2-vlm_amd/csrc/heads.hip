@@ -4,6 +4,7 @@
 // projection heads + F.normalize (xvlm.py:785-792), ITC / ITM / MLM cross-entropies
 // (xvlm.py:794-826, 895-899, xbert.py:1660-1661), torch.multinomial hard negatives (xvlm.py:828-857).
 #include "x2_common.h"
+#include "x2_negatives.h"   // block_reduce, sample_negatives_row
 #define SCATTER_MAX_R_E 8192        // rows marked per pass of the embedding backward's bitmap
 
 // ------------------------------------------------------------------------------------ embeddings
@@ -301,16 +302,6 @@ extern "C" int x2_l2norm(const float* x, const float* dy, float* out, int R, int
 
 // ------------------------------------------------------------------------------------ softmax cross-entropy
 // One workgroup per row.  fwd: lse[r], loss_row[r] = lse - logit[label] (0 and not counted when label == ignore).
-__device__ __forceinline__ float block_reduce(float v, float* sh, bool is_max) {
-  v = is_max ? wave_max(v) : wave_sum(v);
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  __syncthreads();
-  if (l == 0) sh[w] = v;
-  __syncthreads();
-  float r = sh[0];
-  for (int i = 1; i < (int)(blockDim.x >> 6); ++i) r = is_max ? fmaxf(r, sh[i]) : r + sh[i];
-  return r;
-}
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ logits, long ld, const long* __restrict__ labels, int C,
                                                      float* lse, float* loss_row) {
   __shared__ float sh[8];
@@ -399,36 +390,10 @@ extern "C" int x2_ce_bwd(const float* logits, long ld, const long* labels, const
 }
 
 // ------------------------------------------------------------------------------------ hard negatives
-// Row b: w[j] = softmax_j(sim[b][j]) + 1e-5, w[b] = 0 (or w[j] = 0 where group[j] == group[b]); draw one j
-// with the uniform u[b] in [0,1) by inverse CDF.  One workgroup (<= 1024 columns) per row; no host sync.
+// the draw itself is x2_negatives.h's sample_negatives_row (shared with x2_sample_negatives_checked, retrieval.hip)
 __global__ __launch_bounds__(256) void sample_negatives_kernel(const float* __restrict__ sim, int n, const long* __restrict__ group,
                                                                const float* __restrict__ u, int* out) {
-  __shared__ float sh[8];
-  __shared__ float w[1024];
-  const int b = blockIdx.x;
-  const float* z = sim + (long)b * n;
-  float mx = -INFINITY;
-  for (int c = threadIdx.x; c < n; c += 256) mx = fmaxf(mx, z[c]);
-  mx = block_reduce(mx, sh, true);
-  float s = 0.f;
-  for (int c = threadIdx.x; c < n; c += 256) s += __expf(z[c] - mx);
-  s = block_reduce(s, sh, false);
-  for (int c = threadIdx.x; c < n; c += 256) {
-    const bool same = group ? group[c] == group[b] : c == b;
-    w[c] = same ? 0.f : __expf(z[c] - mx) / s + 1e-5f;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tot = 0.f;
-    for (int c = 0; c < n; ++c) tot += w[c];
-    const float t = u[b] * tot;
-    float cum = 0.f; int pick = -1;
-    for (int c = 0; c < n; ++c) { cum += w[c]; if (w[c] > 0.f && cum > t) { pick = c; break; } }
-    if (pick < 0) for (int c = n - 1; c >= 0; --c) if (w[c] > 0.f) { pick = c; break; }
-    // every candidate masked (all rows in one group): torch.multinomial raises in the reference (xvlm.py:845-855); the
-    // host rejects that batch (XVLMBase.get_hard_negatives).  Never hand an out-of-range row index downstream.
-    out[b] = pick < 0 ? b : pick;
-  }
+  sample_negatives_row(sim, n, group, u, out, nullptr);
 }
 extern "C" int x2_sample_negatives(const float* sim, int n, const long* group, const float* u, int* out, void* stream) {
   X2_REQUIRE(n > 1 && n <= 1024, "x2_sample_negatives: n=%d not in (1,1024]", n);

@@ -1301,3 +1301,61 @@ def cls_accuracy_rows(logits, labels, counts, C=None):
     out = torch.empty(2, R, device=logits.device, dtype=torch.int32)
     call("x2_cls_accuracy_rows", ptr(logits), ldl, ptr(labels), R, C, ptr(out[0]), ptr(out[1]), ptr(counts))
     return out[0], out[1]
+
+
+# ----------------------------------------------------------------------------- image-text retrieval (csrc/retrieval.hip)
+
+def _is_group_ids(idx, N, dev):
+    return idx.dtype == torch.int64 and idx.shape == (N,) and idx.is_contiguous() and idx.device == dev
+
+
+def itc_soft_fwd(logits, idx):
+    """The soft-label contrastive loss of get_contrastive_loss(idx=...) on fp32 logits [N, >= N] (already divided by temp) and the gathered group
+    ids idx int64 [N] -> (out fp32 [1] = (mean_i li_i + mean_j lt_j) / 2, rowstat [N, 3], colstat [N, 3] = {max, log-sum, cnt}, loss_rows [2N] =
+    {li, lt}).
+    Two launches, no read-back."""
+    N = logits.shape[0]
+    ld = _f32_rows(logits, N, "logits")
+    assert _is_group_ids(idx, N, logits.device)
+    buf = torch.empty(8 * N + 1, device=logits.device, dtype=F32)
+    rowstat, colstat, loss_rows, out = buf[:3 * N].view(N, 3), buf[3 * N:6 * N].view(N, 3), buf[6 * N:8 * N], buf[8 * N:]
+    call("x2_itc_soft_fwd", ptr(logits), ld, ptr(idx), N, ptr(rowstat), ptr(colstat), ptr(loss_rows), ptr(out))
+    return out, rowstat, colstat, loss_rows
+
+
+def itc_soft_bwd(logits, idx, rowstat, colstat, g, dlogits=None):
+    """dlogits fp32 [N, N] of itc_soft_fwd for the device scalar g; rowstat / colstat are the forward's.  One launch."""
+    N = logits.shape[0]
+    ld = _f32_rows(logits, N, "logits")
+    assert _is_group_ids(idx, N, logits.device) and _is_dev_scalar(g, logits.device)
+    assert rowstat.shape == (N, 3) and colstat.shape == (N, 3) and rowstat.is_contiguous() and colstat.is_contiguous()
+    if dlogits is None:
+        dlogits = torch.empty(N, N, device=logits.device, dtype=F32)
+    ldd = _f32_rows(dlogits, N, "dlogits")
+    call("x2_itc_soft_bwd", ptr(logits), ld, ptr(idx), N, ptr(rowstat), ptr(colstat), ptr(g), ptr(dlogits), ldd)
+    return dlogits
+
+
+def sample_negatives_checked(sim, u, group=None):
+    """sample_negatives (the same device code, the same bits) -> (out int32 [n], no_negative int32 [n]: 1 where every candidate of the row is
+    masked; out[b] = b there)."""
+    n = sim.shape[0]
+    buf = torch.empty(2, n, device=sim.device, dtype=torch.int32)
+    call("x2_sample_negatives_checked", ptr(sim), n, ptr(group), ptr(u), ptr(buf[0]), ptr(buf[1]))
+    return buf[0], buf[1]
+
+
+def retrieval_ranks(scores, gt_offs, gt_ids, counts, N=None):
+    """ranks int32 [R] = per query row of fp32 scores [R, >= N] the least, over its ground-truth columns gt_ids[gt_offs[r] .. gt_offs[r+1]) (int32
+    CSR), number of columns c < N scoring STRICTLY higher; INT_MAX without a ground truth.  counts int64 [4] += {#ranks < 1, < 5, < 10, R}.
+    Two launches, no read-back.  The caller guarantees 0 <= gt_offs[r] <= gt_offs[r+1] <= len(gt_ids)."""
+    R = scores.shape[0]
+    N = scores.shape[1] if N is None else N
+    ld = _f32_rows(scores, N, "scores")
+    dev = scores.device
+    assert gt_offs.dtype == torch.int32 and gt_offs.shape == (R + 1,) and gt_offs.is_contiguous() and gt_offs.device == dev
+    assert gt_ids.dtype == torch.int32 and gt_ids.dim() == 1 and gt_ids.is_contiguous() and gt_ids.device == dev
+    assert counts.dtype == torch.int64 and counts.shape == (4,) and counts.is_contiguous() and counts.device == dev
+    ranks = torch.empty(R, device=dev, dtype=torch.int32)
+    call("x2_retrieval_ranks", ptr(scores), ld, R, N, ptr(gt_offs), ptr(gt_ids) if gt_ids.numel() else None, ptr(ranks), ptr(counts))
+    return ranks

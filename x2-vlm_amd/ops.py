@@ -267,3 +267,47 @@ def cls_wide(seq, h, *, targets=None, offs=None, weights=None, teacher=None, den
         if offs.shape != (R + 1,) or (weights is not None and weights.shape != targets.shape):
             raise ValueError("ops.cls_wide: offs must be [R + 1] and weights as long as targets")
     return _ClsWide.apply(h, seq[1].weight, seq[1].bias, seq[3].weight, seq[3].bias, seq[1].eps, offs, targets, weights, teacher, denom_mode)
+
+
+class _ItcSoft(torch.autograd.Function):
+    """The soft-label contrastive loss (xvlm.py:805-826) as kernels.itc_soft_fwd / _bwd: two launches forward, one backward.  Kept for the
+    backward: the logits, the ids and the per-row / per-column {lse, cnt}.  Nothing is read back, so the function can be captured."""
+
+    @staticmethod
+    def forward(ctx, logits, idx):
+        out, rowstat, colstat, _ = K.itc_soft_fwd(logits, idx)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(logits, idx, rowstat, colstat)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, idx, rowstat, colstat = ctx.saved_tensors
+        if g is None:
+            return None, None
+        return K.itc_soft_bwd(logits, idx, rowstat, colstat, g.to(torch.float32).reshape(1).contiguous()), None
+
+
+def itc_soft(logits, idx_all):
+    """(mean_i CE(logits[i], lab[i]) + mean_j CE(logits[:, j], lab[j])) / 2 with lab = pos / pos.sum(1), pos = (idx_all == idx_all^T): the `idx`
+    branch of XVLMBase.get_contrastive_loss on fp32 logits [N, N] (similarities / temp, 2 <= N <= 1024) and the gathered ids [N].
+    Differentiable in logits; nothing is read back."""
+    require_hip(logits, "ops.itc_soft")
+    require_hip(idx_all, "ops.itc_soft")
+    if logits.dim() != 2 or logits.shape[0] != logits.shape[1] or idx_all.numel() != logits.shape[0]:
+        raise ValueError("ops.itc_soft: logits must be [N, N] and idx_all hold N ids (got %s and %d)" % (tuple(logits.shape), idx_all.numel()))
+    logits = logits.to(torch.float32)
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    return _ItcSoft.apply(logits, idx_all.detach().to(torch.int64).reshape(-1).contiguous())
+
+
+def retrieval_ranks(scores, gt_offs, gt_ids, counts):
+    """ranks int32 [R] of fp32 device scores [R, N] under the CSR ground truths (gt_offs int32 [R + 1], gt_ids int32), counts int64 [4] +=
+    {#ranks < 1, #ranks < 5, #ranks < 10, R}: kernels.retrieval_ranks (rank = the number of STRICTLY greater scores; INT_MAX without a ground
+    truth).  No read-back."""
+    require_hip(scores, "ops.retrieval_ranks")
+    scores = scores.detach().to(torch.float32)
+    if scores.stride(1) != 1:
+        scores = scores.contiguous()
+    return K.retrieval_ranks(scores, gt_offs, gt_ids, counts)

@@ -230,14 +230,10 @@ class XVLMBase(nn.Module):
         if idx is None:
             labels = torch.arange(n, device=logits.device)
             return (ops.cross_entropy(logits, labels) + ops.cross_entropy(logits.t(), labels)) / 2
-        idx = idx.view(-1, 1)
-        idx_all = allgather(idx)
-        pos = torch.eq(idx_all, idx_all.t()).float()
-        lab = pos / pos.sum(1, keepdim=True)
-        # soft-label branch (fine-tuning only, not on the pre-training hot path): plain torch log-softmax
-        li = -torch.sum(torch.log_softmax(logits, dim=1) * lab, dim=1).mean()
-        lt = -torch.sum(torch.log_softmax(logits.t(), dim=1) * lab, dim=1).mean()
-        return (li + lt) / 2
+        # soft-label branch (retrieval fine-tuning): rows sharing an id are each other's positives.  Under DDP every rank computes the full
+        # [N_all, N_all] loss from the gathered features and ids, as the reference does (xvlm.py:805-826); csrc/retrieval.hip, no read-back
+        assert idx.size(0) == image_feat.size(0)
+        return ops.itc_soft(logits, allgather(idx.view(-1, 1)).view(-1))
 
     def get_hard_negatives(self, image_feat, text_feat, idx=None):
         """xvlm.py:828-857 without the 2*B host syncs: one batched inverse-CDF draw per direction on
@@ -251,12 +247,22 @@ class XVLMBase(nn.Module):
             sim_i2t = K.linear_f32(fi, ft, alpha_ptr=None) / temp
             sim_t2i = K.linear_f32(ft, fi, alpha_ptr=None) / temp
             u = torch.rand(2, bs, device=fi.device)
-            grp = idx.view(-1).long().contiguous() if idx is not None else None
-            if grp is not None and bool((grp.view(-1, 1) == grp.view(1, -1)).all(1).any()):
-                # fine-tuning path only (one host sync; the reference has 2*B there): a row whose every candidate shares its
-                # `idx` has no negative to draw - torch.multinomial raises on the all-zero weights (xvlm.py:845-855)
+            if idx is None:
+                return K.sample_negatives(sim_t2i, u[0].contiguous(), None), K.sample_negatives(sim_i2t, u[1].contiguous(), None)
+            # fine-tuning path: a row whose every candidate shares its `idx` has no negative to draw - torch.multinomial raises on the all-zero
+            # weights (xvlm.py:845-855).  The checked sampler flags such rows on the device (by idx both directions flag the same rows; a row
+            # of NaN similarities is flagged in its own direction, so the two are merged) and hands back the in-range fallback b.  Eagerly
+            # the flags are read once (the reference has 2*B syncs there) and the batch is refused; while a stream capture is in progress
+            # nothing is read back: last_no_negative and last_negatives stay on the device for the caller to inspect after a replay, and a
+            # flagged row trains on the pair (b, b).
+            grp = idx.view(-1).long().contiguous()
+            ineg, no_image = K.sample_negatives_checked(sim_t2i, u[0].contiguous(), grp)
+            tneg, no_text = K.sample_negatives_checked(sim_i2t, u[1].contiguous(), grp)
+            flags = torch.maximum(no_image, no_text)
+            self.last_no_negative, self.last_negatives = flags, (ineg, tneg)
+            if not torch.cuda.is_current_stream_capturing() and flags.any():
                 raise RuntimeError("get_hard_negatives: a row has no candidate with a different idx (invalid multinomial distribution)")
-            return K.sample_negatives(sim_t2i, u[0].contiguous(), grp), K.sample_negatives(sim_i2t, u[1].contiguous(), grp)
+            return ineg, tneg
 
     def get_matching_loss(self, image_embeds, image_atts, image_feat, text_embeds, text_atts, text_feat, idx=None):
         """xvlm.py:859-899: B positives + 2B hard negatives as ONE 3B-row fusion pass."""
