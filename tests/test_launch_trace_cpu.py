@@ -3,8 +3,8 @@ model code runs on plain CPU tensors without the library.  Per call the recorder
 its declared type in _lib._SIGS: scalars by value (floats to 6 significant digits), pointers as "null" / "ptr", an AttnArgs block as the dict
 of its fields under the same rule, ctypes arrays by length.  Every scenario's trace must equal tests/golden/launch_trace.json exactly: the
 sequence of entry points a path calls and their scalar arguments are part of its contract (the decode step restates the training layer's
-launches, and the MLM loss, the decode step and VQA ranking run the same LM-head transform: a change to one of them that the others do not
-follow shows up here).
+launches, and the MLM loss, the per-sequence LM loss, the decode step and VQA ranking run the same LM-head transform and - the two losses -
+the same head backward: a change to one of them that the others do not follow shows up here).
 
 The fixture is written by `python tests/test_launch_trace_cpu.py --write`; regenerating it after a change of the traced code proves nothing -
 it is regenerated only when a launch sequence is MEANT to change, and the diff of the fixture is then the review's subject.
@@ -78,6 +78,13 @@ def _config(m, layers=2, fusion_layer=1, width=WIDTH):
 def _ids(rows, cols, seed):
     g = torch.Generator().manual_seed(seed)
     return torch.randint(4, V, (rows, cols), generator=g)
+
+
+def _head_params(model):
+    """(eps, dense weight, dense bias, LayerNorm weight, LayerNorm bias, decoder bias, tied word embeddings) of a model's LM head"""
+    pr = model.cls.predictions
+    return (model.config.layer_norm_eps, pr.transform.dense.weight, pr.transform.dense.bias, pr.transform.LayerNorm.weight,
+            pr.transform.LayerNorm.bias, pr.bias, model.bert.embeddings.word_embeddings.weight)
 
 
 def _scenarios(m, rec):
@@ -162,30 +169,71 @@ def _scenarios(m, rec):
             m.engine.AUX.enabled = False
     with torch.no_grad():
         scenario("bert_eval_mask2d_aux_ahead", aux_ahead)
+
+    # 8. the backward passes of the two LM losses and of the MLP heads: `name` (None: not kept, an earlier scenario holds it) is the forward
+    #    from an emptied bank, `name_backward` (or `backward`) what scalar_of(its result).backward() launches behind it
+    def with_backward(name, fn, scalar_of, backward=None):
+        m.engine.BANK.invalidate()
+        rec.take()
+        res = fn()
+        fwd = rec.take()
+        if name is not None:
+            out[name] = fwd
+        scalar_of(res).backward()
+        out[backward or name + "_backward"] = rec.take()
+
+    word = te.bert.embeddings.word_embeddings.weight
+    seq_g = seq.clone().requires_grad_()
+    with_backward(None, lambda: te.mlm_loss_from_hidden(seq_g, masked_pos, labels), lambda r: r[0], backward="mlm_loss_backward")
+    assert seq_g.grad is not None and word.grad is not None
+    with_backward(None, lambda: te.smoothed_mlm_loss_from_hidden(seq_g, masked_pos, labels.clamp(min=1), weights, 1, 0.1), lambda r: r[0],
+                  backward="mlm_loss_smoothed_backward")
+
+    # ... with the word-embedding gradient parked for the embedding backward instead of returned (the segmented step's route)
+    word.grad = None
+    with pytest.MonkeyPatch.context() as tie:
+        tie.setattr(m.engine, "TIE_WORD_GRAD", True)
+        try:
+            with_backward(None, lambda: te.mlm_loss_from_hidden(seq_g, masked_pos, labels), lambda r: r[0], backward="mlm_loss_backward_tied")
+            assert len(m.engine._TIED_DWORD) == 1 and word.grad is None
+        finally:
+            m.engine._TIED_DWORD.clear()
+
+    # 9. the per-sequence LM loss of the answer decoder: the 6 rows as 2 sequences of 3 scored positions
+    head = _head_params(dec)
+    rows_g = rows.float().requires_grad_()
+    c = torch.tensor([0.5, 0.25])
+    with_backward("lm_seq_loss", lambda: m.engine.SeqLmLossFn.apply(rows_g, labels, 3, c, *head), lambda r: r[1])
+    with_backward(None, lambda: m.engine.SeqLmLossFn.apply(rows_g, labels, 3, None, *head), lambda r: r[0].sum(),
+                  backward="lm_seq_loss_unweighted_backward")
+
+    # 10. a build_mlp head on 4 rows: input width 128 takes the bf16 MFMA first layer, 100 (no multiple of 64) the fp32 one
+    ops, xvlm = importlib.import_module("x2-vlm_amd.ops"), importlib.import_module("x2-vlm_amd.xvlm")
+    for kind, width in (("mfma", 128), ("f32", 100)):
+        mlp = xvlm.build_mlp(width, 2)
+        x = torch.randn(4, width, generator=torch.Generator().manual_seed(9)).requires_grad_()
+        with_backward("mlp_head_" + kind, lambda: ops.mlp_head(mlp, x), lambda y: y.sum())
+        with torch.no_grad():
+            scenario("head_first_linear_" + kind, lambda: ops.head_first_linear(mlp, x))
     return out
 
 
 def record_all():
+    """Every scenario, recorded from the code as it stands: kernels.call replaced by the recorder, and kernels.raw_stream - workspace() asks
+    it, and the real one initialises the GPU - by a constant."""
     m = _mods()
     rec = Recorder(m.lib)
-    saved = m.kernels.call
-    m.kernels.call = rec
-    try:
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(m.kernels, "call", rec)
+        mp.setattr(m.kernels, "raw_stream", lambda: 0)
         return _scenarios(m, rec)
-    finally:
-        m.kernels.call = saved
 
 
 # ----------------------------------------------------------------------------- the tests
 
 @pytest.fixture(scope="module")
 def recorded():
-    """Every scenario, recorded once from the code as it stands (kernels.call replaced through pytest's MonkeyPatch)."""
-    m = _mods()
-    rec = Recorder(m.lib)
-    with pytest.MonkeyPatch.context() as mp:
-        mp.setattr(m.kernels, "call", rec)
-        return _scenarios(m, rec)
+    return record_all()
 
 
 def test_every_launch_trace_equals_the_fixture(recorded):
@@ -241,6 +289,41 @@ def test_second_stream_projects_the_same_kv_ahead_of_the_layers(recorded):
     moved = list(inline)
     moved.insert(first, moved.pop(kv[0]))
     assert ahead == moved
+
+
+LM_HEAD_BACKWARD = ["x2_colsum_bf16", "x2_gemm_nt_splitk", "x2_layernorm_bwd", "x2_gelu_f32", "x2_cast_bf16", "x2_colsum_bf16", "x2_gemm_nt",
+                    "x2_gemm_tn_grouped"]
+
+
+def test_the_two_lm_losses_share_the_head(recorded):
+    """MlmLossFn and SeqLmLossFn differ in the loss only: in front of the fused decoder GEMM both run one transform (dense + GELU, LayerNorm,
+    the casts of the tied decoder), behind the kernel that writes the logit gradient both run one backward - call for call with the same
+    arguments, the two scenarios having 6 rows each.  The MLM loss alone gathers its rows, so its backward alone ends with their scatter."""
+    mlm, seq = recorded["mlm_loss"], recorded["lm_seq_loss"]
+    first = [c[0] for c in mlm].index("x2_cast_bf16")
+    assert [c[0] for c in mlm[:first]] == ["x2_gather_rows"]
+    assert seq[:-2] == mlm[first:-2]
+    assert seq[-2] == mlm[-2] and seq[-2][0] == "x2_mlm_ce_fwd"                # stage 1 of both losses; the combine launches differ
+    assert [seq[-1][0], mlm[-1][0]] == ["x2_seq_loss_combine", "x2_ce_combine"]
+    mlm_b, seq_b = recorded["mlm_loss_backward"], recorded["lm_seq_loss_backward"]
+    assert [c[0] for c in mlm_b] == ["x2_mlm_ce_bwd"] + LM_HEAD_BACKWARD + ["x2_scatter_rows"]
+    assert [c[0] for c in seq_b] == ["x2_mlm_seq_bwd"] + LM_HEAD_BACKWARD
+    assert seq_b[1:] == mlm_b[1:-1]
+    for other, first_call in (("mlm_loss_smoothed_backward", "x2_mlm_ls_bwd"), ("lm_seq_loss_unweighted_backward", "x2_mlm_seq_bwd")):
+        assert recorded[other][0][0] == first_call and recorded[other][1:len(seq_b)] == seq_b[1:], other
+
+
+def test_parking_the_word_gradient_launches_nothing_else(recorded):
+    """engine.TIE_WORD_GRAD only changes where the tied decoder's gradient goes (the scenario asserts that it is parked in engine._TIED_DWORD
+    and that the word embeddings receive none)"""
+    assert recorded["mlm_loss_backward_tied"] == recorded["mlm_loss_backward"]
+
+
+@pytest.mark.parametrize("kind", ["mfma", "f32"])
+def test_head_first_linear_is_how_mlp_head_starts(recorded, kind):
+    first, whole = recorded["head_first_linear_" + kind], recorded["mlp_head_" + kind]
+    assert first[-1][0] == ("x2_gemm_nt" if kind == "mfma" else "x2_linear_f32")
+    assert 0 < len(first) < len(whole) and whole[:len(first)] == first
 
 
 def _dump(traces, path):

@@ -959,20 +959,28 @@ def logprob_topk(logits, V, k, *, seq=None, seq_len=0, ngram=0, eos_id=0, forbid
 
 # ----------------------------------------------------------------------------- VQA inference (csrc/vqa.hip)
 
-def mlm_ce_rows(x, E, bias, labels, V):
-    """The per-row half of mlm_ce_fwd: -> (loss_row fp32 [R] = lse - z[label], 0 where the label is negative; lse fp32 [R]) of z = x @ E^T + bias
-    over the first V columns, the logits never stored."""
+def _mlm_stage1(x, E, bias, labels, V, nsmall):
+    """The stage-1 launch mlm_ce_fwd starts with (the pre-training step's wrapper keeps its own statement of it), for the fine-tune losses.
+    -> (part fp32 [R, Vp / 64, 2], zlab fp32 [R], rest fp32 [nsmall]: room for what the caller's combine launch writes, one allocation)."""
     assert x.dtype == BF16 and E.dtype == BF16 and x.shape[1] == E.shape[1] and bias.dtype == F32 and bias.numel() == E.shape[0]
     assert labels.dtype == torch.int64 and labels.numel() == x.shape[0]
     R, Hd = x.shape
     Vp = E.shape[0]
-    dev = x.device
-    part = torch.empty(R, Vp // 64, 2, device=dev, dtype=F32)
-    small = torch.empty(3 * R + 2, device=dev, dtype=F32)
-    zlab, lse, rows, stat = small[:R], small[R:2 * R], small[2 * R:3 * R], small[3 * R:]
+    part = torch.empty(R, Vp // 64, 2, device=x.device, dtype=F32)
+    small = torch.empty(R + nsmall, device=x.device, dtype=F32)
+    zlab = small[:R]
     with _timed(2.0 * R * Vp * Hd):
         call("x2_mlm_ce_fwd", ptr(x), ptr(E), ptr(bias), ptr(labels), R, Vp, V, Hd, _rows(x), _rows(E), ptr(part), ptr(zlab))
-    call("x2_ce_combine", ptr(part), Vp // 64, ptr(zlab), ptr(labels), R, ptr(lse), ptr(rows), ptr(stat))
+    return part, zlab, small[R:]
+
+
+def mlm_ce_rows(x, E, bias, labels, V):
+    """The per-row half of mlm_ce_fwd: -> (loss_row fp32 [R] = lse - z[label], 0 where the label is negative; lse fp32 [R]) of z = x @ E^T + bias
+    over the first V columns, the logits never stored."""
+    R = x.shape[0]
+    part, zlab, rest = _mlm_stage1(x, E, bias, labels, V, 2 * R + 2)
+    lse, rows, stat = rest[:R], rest[R:2 * R], rest[2 * R:]
+    call("x2_ce_combine", ptr(part), E.shape[0] // 64, ptr(zlab), ptr(labels), R, ptr(lse), ptr(rows), ptr(stat))
     return rows, lse
 
 
@@ -1047,17 +1055,13 @@ def mlm_seq_fwd(x, E, bias, labels, V, T, c=None):
     """Per-sequence cross-entropy of z = x @ E^T + bias over the first V columns without storing z: rows r = s * T + t of x [S * T, Hd] bf16,
     labels int64 [S * T] (negative: ignored) -> (loss_seq fp32 [S] = sum_t (lse - z[label]) in index order, total fp32 [1] =
     sum_s c[s] * loss_seq[s] or None without c, lse fp32 [S * T])."""
-    assert x.dtype == BF16 and E.dtype == BF16 and x.shape[1] == E.shape[1] and bias.dtype == F32 and bias.numel() == E.shape[0]
-    assert labels.dtype == torch.int64 and labels.numel() == x.shape[0] and x.shape[0] % T == 0
-    R, Hd = x.shape
-    S, Vp, dev = R // T, E.shape[0], x.device
-    assert c is None or (c.dtype == F32 and c.numel() == S and c.is_contiguous())
-    part = torch.empty(R, Vp // 64, 2, device=dev, dtype=F32)
-    small = torch.empty(2 * R + S + 1, device=dev, dtype=F32)
-    zlab, lse, loss_seq, total = small[:R], small[R:2 * R], small[2 * R:2 * R + S], small[2 * R + S:]
-    with _timed(2.0 * R * Vp * Hd):
-        call("x2_mlm_ce_fwd", ptr(x), ptr(E), ptr(bias), ptr(labels), R, Vp, V, Hd, _rows(x), _rows(E), ptr(part), ptr(zlab))
-    call("x2_seq_loss_combine", ptr(part), Vp // 64, ptr(zlab), ptr(labels), S, T, ptr(c), ptr(lse), ptr(loss_seq), ptr(total) if c is not None else None)
+    R = x.shape[0]
+    S = R // T
+    assert R % T == 0 and (c is None or (c.dtype == F32 and c.numel() == S and c.is_contiguous()))
+    part, zlab, rest = _mlm_stage1(x, E, bias, labels, V, R + S + 1)
+    lse, loss_seq, total = rest[:R], rest[R:R + S], rest[R + S:]
+    call("x2_seq_loss_combine", ptr(part), E.shape[0] // 64, ptr(zlab), ptr(labels), S, T, ptr(c), ptr(lse), ptr(loss_seq),
+         ptr(total) if c is not None else None)
     return loss_seq, (total if c is not None else None), lse
 
 

@@ -243,15 +243,19 @@ class BertOnlyMLMHead(nn.Module):
 
 
 class LMHeadRows:
-    """The LM head `cls` (transform + decoder tied to the word embeddings of `bert`) applied to gathered bf16 rows at inference, for the two
-    models that carry one."""
+    """The LM head `cls` (transform + decoder tied to the word embeddings of `bert`) of the two models that carry one: its parameters as the
+    engine takes them, and the head applied to gathered bf16 rows at inference."""
+
+    def head_params(self):
+        """(eps, dense weight, dense bias, LayerNorm weight, LayerNorm bias, decoder bias, tied word embeddings): the head as
+        engine.lm_head_transform and the two loss Functions take it"""
+        pr = self.cls.predictions
+        return (self.config.layer_norm_eps, pr.transform.dense.weight, pr.transform.dense.bias, pr.transform.LayerNorm.weight,
+                pr.transform.LayerNorm.bias, pr.bias, self.bert.embeddings.word_embeddings.weight)
 
     def _head(self, rows):
         """-> (transformed bf16 rows [R, Hd], padded bf16 embeddings [Vp, Hd], padded bias [Vp]) of bf16 hidden rows [R, Hd]"""
-        pr = self.cls.predictions
-        tb, _, _, _, _, Eb, _, bias_p = lm_head_transform(rows, self.config.layer_norm_eps, pr.transform.dense.weight, pr.transform.dense.bias,
-                                                          pr.transform.LayerNorm.weight, pr.transform.LayerNorm.bias, pr.bias,
-                                                          self.bert.embeddings.word_embeddings.weight)
+        tb, _, _, _, _, Eb, _, bias_p = lm_head_transform(rows, *self.head_params())
         return tb, Eb, bias_p
 
     def head_logits(self, rows):
@@ -296,11 +300,9 @@ class BertForMaskedLM(nn.Module, LMHeadRows):
         B, L, Hd = sequence_output.shape
         flat = (torch.arange(B, device=masked_pos.device).unsqueeze(1) * L + masked_pos).reshape(-1)
         rows = ops.gather_rows(sequence_output.reshape(B * L, Hd), flat)
-        pr = self.cls.predictions
         w = weights.reshape(-1).to(torch.float32).contiguous()
-        return MlmLossFn.apply(rows, labels, self.config.layer_norm_eps, keep_logits, pr.transform.dense.weight, pr.transform.dense.bias,
-                               pr.transform.LayerNorm.weight, pr.transform.LayerNorm.bias, pr.bias,
-                               self.bert.embeddings.word_embeddings.weight, (w, int(ignore_index), float(label_smoothing)))
+        head = self.head_params()
+        return MlmLossFn.apply(rows, labels, head[0], keep_logits, *head[1:], (w, int(ignore_index), float(label_smoothing)))
 
     def forward(self, input_ids=None, attention_mask=None, encoder_hidden_states=None, encoder_attention_mask=None,
                 labels=None, return_dict=True, mode="multi_modal", masked_pos=None, return_logits=False, position_ids=None, **unused):
@@ -374,9 +376,7 @@ class BertLMHeadModel(nn.Module, LMHeadRows):
         nxt = _next_labels if _next_labels is not None else labels[:, 1:]
         nxt = nxt.to(torch.int64).reshape(-1).contiguous()
         rows = ops.gather_rows(h.reshape(S * L, -1), self._scored_rows(S, L, h.device))
-        pr = self.cls.predictions
-        head = (self.config.layer_norm_eps, pr.transform.dense.weight, pr.transform.dense.bias, pr.transform.LayerNorm.weight,
-                pr.transform.LayerNorm.bias, pr.bias, self.bert.embeddings.word_embeddings.weight)
+        head = self.head_params()
         total = None
         if reduction == "none" or _seq_weights is not None:
             loss, total = SeqLmLossFn.apply(rows, nxt, L - 1, _seq_weights, *head)
